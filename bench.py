@@ -1,11 +1,17 @@
 """Benchmark: co-visitation build over synthetic OTTO-shaped sessions on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--events E]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--events E] [--dump-outputs DIR] [--full]
 
 One step = one full co-visitation build of BASELINE.json configs[1]: all five rules over
 ~220M events (100k-session files) -> per-(rule, aid, aid_next) count and count_ge2 tables
 resident in HBM (model/count_co_events.py:80-100 + the cross-file groupby of :168).
 Inputs are resident in HBM before the timed region. Prints one JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line. --dump-outputs DIR then
+also writes the last timed step's tables as DIR/<name>.npy (dump_outputs). --full adds everything
+measured beside the line: the per-phase timing step and its rooflines, A6, the event ingest, the
+CPU baselines, the kNN (configs[2]) and candidates (configs[4]) sub-objects; the --no-* /
+--knn-steps / --cand-steps switches select among those.
 """
 from __future__ import annotations
 
@@ -298,12 +304,75 @@ def bench_candidates(n_sessions: int, steps: int, kmeans_iter: int, group=None, 
             "data": "synthetic (otto-synth seed 0, embeddings seeds 1/3, labels by the OTTO protocol)"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 1_500_000  # expected rows of the sample over all rules (4 float64 columns: 48 MB)
+
+
+def sample_hash(a, b, seed: int):
+    """32-bit hash of the key (aid, aid_next) under `seed`; a, b: int64 torch tensors or numpy arrays with
+    0 <= value < 2^21 (every intermediate stays below 2^63, so both give the same bits)."""
+    x = a * 0x9E3779B1 + b * 0x85EBCA6B + (seed + 1) * 0xC2B2AE35
+    x = ((x ^ (x >> 15)) & 0xFFFFFFFF) * 0x2C1B3C6D
+    return (x >> 13) & 0xFFFFFFFF
+
+
+def dump_outputs(tab, out_dir: str, seed: int, prefix: str = "") -> dict:
+    """Write what the last timed step returned (its count tables, still resident) as out_dir/<name>.npy, float64:
+      <rule>.npy         rows (aid, aid_next, count, count_ge2) of a fixed sample of the rule's table, sorted by
+                         (aid, aid_next). A row is kept by a hash of (aid, aid_next, seed) alone, so the sample does
+                         not depend on the order the build leaves its rows in: two builds on the same input sample
+                         the same keys. The whole table where it is small enough.
+      <rule>_digest.npy  ottohip_table_digest over every row of the rule (d_count, d_count_ge2, pairs, pairs_ge2,
+                         rows): each wrapping u64 as four 16-bit limbs, low first (exact in float64).
+      stats.npy          per rule (n_rows, n_pairs, file_rows, file_rows_ge2).
+    All files together stay below DUMP_MAX_BYTES."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    stats = {n: tab.stats(n) for n in tab.names}
+    total = max(sum(s["n_rows"] for s in stats.values()), 1)
+    thr = min(1 << 32, (DUMP_SAMPLE_ROWS << 32) // total)  # keep a row whose 32-bit hash is below thr
+    cap = (DUMP_MAX_BYTES - (1 << 20)) // 32               # rows of all rules together (32 B each)
+    chunk = 1 << 27
+    written = 0
+
+    def save(name, arr):
+        nonlocal written
+        path = os.path.join(out_dir, f"{prefix}{name}.npy")
+        np.save(path, np.ascontiguousarray(arr, dtype=np.float64))
+        written += os.path.getsize(path)
+
+    for n in tab.names:
+        a, b, c, c2 = tab.to_torch(n)
+        keep = []
+        for i in range(0, a.numel(), chunk):
+            h = sample_hash(a[i:i + chunk].to(torch.int64), b[i:i + chunk].to(torch.int64), seed)
+            keep.append(torch.nonzero(h < thr).squeeze(1) + i)
+        idx = torch.cat(keep) if keep else torch.zeros(0, dtype=torch.int64, device=a.device)
+        rows = torch.stack([a[idx].to(torch.int64), b[idx].to(torch.int64), c[idx].to(torch.int64) & 0xFFFFFFFF,
+                            c2[idx].to(torch.int64) & 0xFFFFFFFF], 1).cpu().numpy()
+        del a, b, c, c2, keep, idx
+        rows = rows[np.lexsort((rows[:, 1], rows[:, 0]))]
+        save(n, rows[:cap * stats[n]["n_rows"] // total + 1])
+        d = tab.digest(n)
+        save(f"{n}_digest", [[(d[k] >> s) & 0xFFFF for s in (0, 16, 32, 48)]
+                             for k in ("d_count", "d_count_ge2", "pairs", "pairs_ge2", "rows")])
+    save("stats", [[stats[n][k] for k in ("n_rows", "n_pairs", "file_rows", "file_rows_ge2")] for n in tab.names])
+    torch.cuda.empty_cache()
+    assert written <= DUMP_MAX_BYTES, written
+    return {"dir": out_dir, "bytes": written, "sample_hash_below": thr}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--events", type=int, default=220_000_000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's count tables as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside the line: phase timing and rooflines, A6, ingest, "
+                         "CPU baselines, the kNN and candidates sub-objects (each with its own --no-* / --*-steps switch)")
     ap.add_argument("--pandas-files", type=int, default=10, help="files of the pandas reference-algorithm baseline")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-a6", action="store_true", help="skip the A6 (concat_files_w_stats) timing beside the line")
@@ -321,6 +390,10 @@ def main():
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="nccl = RCCL over xGMI (the product); gloo = host-staged rehearsal on fewer GPUs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "covis":
+        ap.error("--dump-outputs writes the co-visitation tables: use it with --workload covis")
 
     import torch
     import torch.distributed as dist
@@ -334,7 +407,8 @@ def main():
         return
     if args.workload == "knn":
         torch.cuda.set_device(0)
-        print(json.dumps(bench_knn(max(args.knn_steps, 1), 1, args.knn_items, args.knn_queries, not args.no_cpu)))
+        print(json.dumps(bench_knn(max(args.knn_steps, 1), 1, args.knn_items, args.knn_queries,
+                                   args.full and not args.no_cpu)))
         return
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -406,23 +480,28 @@ def main():
     stats = {n: tab.stats(n) for n in tab.names}
     pairs = sum(s["n_pairs"] for s in stats.values())
     rows = sum(s["n_rows"] for s in stats.values())
+    dumped = None
+    if args.dump_outputs:  # the last timed step's tables, before anything else runs
+        dumped = dump_outputs(tab, args.dump_outputs, args.seed, f"rank{rank}_" if world > 1 else "")
 
-    # phase timing of one extra (untimed) step with HIP events on the launch stream
-    ctx.set_timing(True)
-    tab.free()
-    tab = step()
-    phases = ctx.timings()
-    ctx.set_timing(False)
+    full = args.full
+    phases = []
+    if full:  # phase timing of one extra (untimed) step with HIP events on the launch stream
+        ctx.set_timing(True)
+        tab.free()
+        tab = step()
+        phases = ctx.timings()
+        ctx.set_timing(False)
     a6 = None
     tab.free()
-    if world == 1 and not args.no_a6:
+    if full and world == 1 and not args.no_a6:
         ctx.trim()  # the build's word buffers
         try:  # reported beside the line; it must not cost the main line
             a6 = bench_a6(dev, ctx)
         except Exception as exc:  # noqa: BLE001
             a6 = {"error": repr(exc)}
     ingest = None
-    if world == 1 and not args.no_ingest:
+    if full and world == 1 and not args.no_ingest:
         ctx.trim()
         try:  # reported beside the line
             ingest = bench_ingest(ev, fb, dev, ctx)
@@ -444,11 +523,11 @@ def main():
         del dev, tab
         ctx.trim()
         torch.cuda.empty_cache()
-        if args.knn_steps > 0:
+        if full and args.knn_steps > 0:
             bench_knn(args.knn_steps, 1, args.knn_items, args.knn_queries, False, dist.group.WORLD)
             ctx.trim()
             torch.cuda.empty_cache()
-        if args.cand_steps > 0:
+        if full and args.cand_steps > 0:
             try:
                 bench_candidates(args.cand_sessions, args.cand_steps, args.kmeans_iter, dist.group.WORLD)
             except Exception:  # noqa: BLE001  (rank 0 reports the error)
@@ -496,11 +575,14 @@ def main():
         "events_per_s": n_events / t_step,
         "step_roofline": {"bound": "hbm", "model_bytes": b_model, "achieved": b_model / t_step / 1e9,
                           "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": b_model / t_step / 1e9 / HBM_PEAK_GBS},
-        "roofline": roof(dom[0]),
-        "phase_rooflines": {ph: roof(ph) for ph in ph_ms if ph in alg},
-        "phases_ms": {p[0]: round(p[1], 3) for p in phases},
         "gen_s": round(gen_s, 1),
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
+    if full:  # from the extra phase-timing step
+        out["roofline"] = roof(dom[0])
+        out["phase_rooflines"] = {ph: roof(ph) for ph in ph_ms if ph in alg}
+        out["phases_ms"] = {p[0]: round(p[1], 3) for p in phases}
     if a6 is not None:
         if "total_ms" in a6:
             cpm = (a6["count_ms"] + a6["total_ms"]) / 1e3
@@ -510,15 +592,15 @@ def main():
         out["a6"] = a6
     if ingest is not None:
         out["ingest"] = ingest
-    if not args.no_cpu and world == 1:
+    if full and not args.no_cpu and world == 1:
         out["cpu_baseline"] = cpu_baseline(args.seed, args.pandas_files)
-    if args.knn_steps > 0:
+    if full and args.knn_steps > 0:
         del dev
         ctx.trim()  # each sub-benchmark starts from an empty workspace (its own buffers only)
         torch.cuda.empty_cache()
         out["knn"] = bench_knn(args.knn_steps, 1, args.knn_items, args.knn_queries, not args.no_cpu and world == 1,
                                dist.group.WORLD if world > 1 else None)
-    if args.cand_steps > 0:
+    if full and args.cand_steps > 0:
         if world > 1 and args.knn_steps == 0:
             del dev
         ctx.trim()

@@ -11,6 +11,6 @@ if [ $# -gt 0 ]; then
 fi
 for run in A1 B1 A2 B2; do
   if [ "${run:0:1}" = A ]; then export $var=$va; else export $var=$vb; fi
-  timeout -k 10 300 python3 -u bench.py --no-cpu --no-ingest --steps 1 --warmup 0 --knn-steps 0 --cand-steps 0 > "$O/a6_$run.log" 2>&1 || { tail -20 "$O/a6_$run.log"; exit 1; }
+  timeout -k 10 300 python3 -u bench.py --full --no-cpu --no-ingest --steps 1 --warmup 0 --knn-steps 0 --cand-steps 0 > "$O/a6_$run.log" 2>&1 || { tail -20 "$O/a6_$run.log"; exit 1; }
   echo "$run $var=${!var}"; python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); a=d['a6']; c=a['per_rule']['click_to_click']; print(a['total_ms_runs'], c['stages_ms'], c['rows_out'])" "$O/a6_$run.log"
 done

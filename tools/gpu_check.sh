@@ -11,7 +11,7 @@ if [ $# -gt 0 ]; then
   tail -3 $O/pytest.log
 fi
 if [ "$mode" = bench ]; then
-  timeout -k 10 600 python3 -u bench.py > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
+  timeout -k 10 600 python3 -u bench.py --full > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
   grep '^{' $O/bench.log | tail -1 > $O/bench.json
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(d['ms_per_step'], d['phases_ms'], d['knn']['phases_ms'], d['candidates']['ms_per_step'], d['a6']['total_ms'])" $O/bench.json
 fi

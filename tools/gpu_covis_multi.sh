@@ -15,6 +15,6 @@ i=0
 for spec in "${specs[@]}" "${specs[@]}"; do
   i=$((i + 1))
   ( IFS=','; for kv in $spec; do export "$kv"; done
-    timeout -k 10 300 python3 -u bench.py --no-cpu --no-a6 --no-ingest --steps 5 --warmup 1 --knn-steps 0 --cand-steps 0 > "$O/b_$i.log" 2>&1 ) || { tail -20 "$O/b_$i.log"; exit 1; }
+    timeout -k 10 300 python3 -u bench.py --full --no-cpu --no-a6 --no-ingest --steps 5 --warmup 1 --knn-steps 0 --cand-steps 0 > "$O/b_$i.log" 2>&1 ) || { tail -20 "$O/b_$i.log"; exit 1; }
   echo "$spec"; python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); print(round(d['ms_per_step'],2), d['phases_ms'])" "$O/b_$i.log"
 done

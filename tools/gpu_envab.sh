@@ -10,6 +10,6 @@ if [ $# -gt 0 ]; then
 fi
 for run in A1 B1 A2 B2; do
   if [ "${run:0:1}" = A ]; then export $var=$va; else export $var=$vb; fi
-  timeout -k 10 300 python3 -u bench.py --no-cpu --no-a6 --no-ingest --steps 5 --warmup 1 --knn-steps 0 --cand-steps 0 > "$O/b_$run.log" 2>&1 || { tail -20 "$O/b_$run.log"; exit 1; }
+  timeout -k 10 300 python3 -u bench.py --full --no-cpu --no-a6 --no-ingest --steps 5 --warmup 1 --knn-steps 0 --cand-steps 0 > "$O/b_$run.log" 2>&1 || { tail -20 "$O/b_$run.log"; exit 1; }
   echo "$run $var=${!var}"; python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); print(round(d['ms_per_step'],2), d['phases_ms'])" "$O/b_$run.log"
 done

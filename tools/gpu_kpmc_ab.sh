@@ -4,7 +4,7 @@
 set -o pipefail
 VAR=$1; O=gpurun_out/$2; K=${3:-.}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-B="bench.py --steps 1 --warmup 0 --knn-steps 0 --cand-steps 0 --no-cpu --no-a6 --no-ingest"
+B="bench.py --full --steps 1 --warmup 0 --knn-steps 0 --cand-steps 0 --no-cpu --no-a6 --no-ingest"
 for v in A B; do
   if [ $v = A ]; then export $VAR=${AV:-1}; else export $VAR=${BV:-0}; fi
   timeout -s KILL 180 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD --output-format csv -d $O/$v -o run -- python3 $B > $O/$v.log 2>&1 || { tail -20 $O/$v.log; exit 1; }

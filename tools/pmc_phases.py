@@ -1,5 +1,5 @@
 """Per-phase HBM traffic of the co-visitation build (and per-launch traffic of k_knn_main) from two
-rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of `bench.py --steps 1 --warmup 0 --knn-steps 1`.
+rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of `bench.py --full --steps 1 --warmup 0 --knn-steps 1`.
 
 FETCH_SIZE / WRITE_SIZE are reported in KiB per dispatch; FETCH_SIZE is doubled
 (MI355X_MICROARCH.md §HBM: gfx950 tallies 128-B read requests at 64 B). Dispatches are cut into
@@ -44,7 +44,7 @@ def phases(disp):
 fetch, write = load(sys.argv[1]), load(sys.argv[2])
 bf, bw = phases(fetch), phases(write)
 n = min(len(bf), len(bw))
-out = {"note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes of bench.py --steps 1 --warmup 0 "
+out = {"note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes of bench.py --full --steps 1 --warmup 0 "
                "--knn-steps 1 --cand-steps 0 --no-cpu --no-a6 --no-ingest; FETCH_SIZE (KiB) doubled per MI355X_MICROARCH.md; bytes per "
                f"build phase averaged over {n} full builds (run with --no-a6 --no-ingest, so no A6 part recounts or other kernels follow a build); k_knn_main per launch; produced by tools/pmc_phases.py"}
 for ph in ("prep_count", "rows", "emit", "reduce"):

@@ -7,5 +7,5 @@ shift || true
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o run -- \
-  python3 bench.py --steps 1 --warmup 1 --no-cpu --knn-steps 0 --cand-steps 0 "$@" > "$out/bench.log" 2>&1
+  python3 bench.py --full --steps 1 --warmup 1 --no-cpu --knn-steps 0 --cand-steps 0 "$@" > "$out/bench.log" 2>&1
 python3 tools/kstats.py "$out/run_kernel_stats.csv" > "$out/summary.txt"
