@@ -1772,9 +1772,9 @@ __device__ __forceinline__ void wave_bitonic_sort(uint32_t (&v)[M]) {
   }
 }
 
-// inclusive scan over elements e = lane*M + m (sum or max)
+// inclusive scan over elements e = lane*M + m (sum or max); returns the scan over the lanes before this one
 template <int M, bool MAX>
-__device__ __forceinline__ void wave_scan_elems(uint32_t (&x)[M]) {
+__device__ __forceinline__ uint32_t wave_scan_elems(uint32_t (&x)[M]) {
 #pragma unroll
   for (int m = 1; m < M; ++m) x[m] = MAX ? (x[m] > x[m - 1] ? x[m] : x[m - 1]) : x[m] + x[m - 1];
   const uint32_t tot = x[M - 1];
@@ -1782,12 +1782,40 @@ __device__ __forceinline__ void wave_scan_elems(uint32_t (&x)[M]) {
   const uint32_t excl = lane_prev(incl);
 #pragma unroll
   for (int m = 0; m < M; ++m) x[m] = MAX ? (x[m] > excl ? x[m] : excl) : x[m] + excl;
+  return excl;
 }
 
 // exclusive value before element e = lane*M + m of a per-element inclusive prefix x
 template <int M>
 __device__ __forceinline__ uint32_t excl_at(const uint32_t (&x)[M], int m, uint32_t lane_prev_tot) {
   return m > 0 ? x[m - 1] : lane_prev_tot;
+}
+
+// A staged row's second word (fold_pass): the running totals of the task's elements up to and including the row's
+// k-run end, E = elements | S = single-word w-runs << 11 | (E - W) << 22 with W = w-run ends. E, S <= 1024 take 11
+// bits each; a k-run end is a w-run end, so W >= 1 there and E - W <= 1023 takes the 10 bits left. Every field is
+// non-decreasing over the rows, so the packed difference of two staged words is the field-wise difference (no
+// borrows): a row's own counts come from its predecessor, a rule's statistics from the first and last of its rows.
+__device__ __forceinline__ uint32_t staged_at(const uint32_t* stgb, uint32_t n) {  // totals over the first n rows
+  const uint32_t x = stgb[n ? n - 1u : 0u];
+  return n ? x : 0u;
+}
+__device__ __forceinline__ uint32_t staged_counts(const uint32_t* stgb, uint32_t i) {  // row i: count | count_ge2 << 16
+  const uint32_t d = stgb[i] - staged_at(stgb, i);
+  const uint32_t cnt = d & 2047u;
+  return cnt | ((cnt - ((d >> 11) & 2047u)) << 16);
+}
+// wave-uniform n: the unpacked difference of the totals over the first n1 and the first n0 rows (scalar registers)
+struct FoldTotals {
+  uint32_t pairs, files, singles;
+};
+__device__ __forceinline__ FoldTotals staged_range(const uint32_t* stgb, uint32_t n0, uint32_t n1) {
+  const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)(staged_at(stgb, n1) - staged_at(stgb, n0)));
+  FoldTotals t;
+  t.pairs = d & 2047u;
+  t.singles = (d >> 11) & 2047u;
+  t.files = t.pairs - (d >> 22);
+  return t;
 }
 
 // The fold of one sorted task (k_agg_sort, k_agg_lds): v holds its <= 64*M words (W_EMPTY past the
@@ -1801,123 +1829,83 @@ __device__ __forceinline__ uint32_t excl_at(const uint32_t (&x)[M], int m, uint3
 // takes no statistics; else FO adds the FileOpts rule's per-file rows (fh) and the per-rule statistics go to sacc.
 template <int M, bool FO, bool PM, bool MIRROR>
 __device__ __forceinline__ uint32_t fold_pass(const uint32_t (&v)[M], uint32_t pl, uint32_t nl, const uint32_t* pt,
-                                          uint32_t ppl, uint32_t pnl, bool pmode, uint64_t obegin, uint32_t olen,
+                                          uint32_t pnl, bool pmode, uint64_t obegin, uint32_t olen,
                                           uint32_t rk, const RulesDev& sR, const Layout& L, const OutRows& O,
                                           const FileOpts& fo, unsigned long long* fh, uint32_t* stgk, uint32_t* stgb,
                                           unsigned long long* sacc) {
   const uint32_t l = lane_id();
   const int F = L.F, A = L.A;
   // (1) run flags from the neighbours (a w-run = one word = one (rule, aid_next, file)):
-  //     X = [w-run end] | [singleton w-run] << 11, summed by one scan (fields <= 1024);
-  //     k-run (rule, aid_next) starts and ends as bit masks over the lane's elements
-  uint32_t a[M], b[M], c[M];
-  uint32_t kst = 0, kend = 0;
+  //     X = [w-run end] | [single-word w-run] << 11, summed by one scan (fields <= 1024);
+  //     k-run (rule, aid_next) ends as a bit mask over the lane's elements
+  uint32_t b[M];
+  uint32_t kend = 0;
 #pragma unroll
   for (int m = 0; m < M; ++m) {
     const uint32_t prv = m > 0 ? v[m - 1] : pl, nxt = m < M - 1 ? v[m + 1] : nl;
     const uint32_t valid = v[m] != W_EMPTY ? 1u : 0u;
     const uint32_t ws = valid & (prv != v[m] ? 1u : 0u);
     const uint32_t we = valid & (nxt != v[m] ? 1u : 0u);
-    c[m] = we | ((ws & we) << 11);
-    b[m] = c[m];
-    uint32_t kbs = (prv >> F) != (v[m] >> F) ? 1u : 0u, kbe = (nxt >> F) != (v[m] >> F) ? 1u : 0u;
+    b[m] = we | ((ws & we) << 11);
+    uint32_t kbe = (nxt >> F) != (v[m] >> F) ? 1u : 0u;
     if constexpr (PM) {
       if (pmode) {  // a k-run is one (key, part)
-        const uint32_t pp = m > 0 ? pt[m - 1] : ppl, pn = m < M - 1 ? pt[m + 1] : pnl;
-        kbs |= pp != pt[m] ? 1u : 0u;
+        const uint32_t pn = m < M - 1 ? pt[m + 1] : pnl;
         kbe |= pn != pt[m] ? 1u : 0u;
       }
     }
-    kst |= (valid & kbs) << m;
     kend |= (valid & kbe) << m;
   }
-  if constexpr (FO && !MIRROR) {  // one per-file row per w-run end of the rule; a singleton w-run has count 1
+  if constexpr (FO && !MIRROR) {  // one per-file row per w-run end of the rule; a single-word w-run has count 1
     if (fo.hist && (int)(rk >> A) == fo.type) {
 #pragma unroll
       for (int m = 0; m < M; ++m)
-        if ((c[m] & 1u) && (v[m] >> (A + F)) == fo.q) {  // a symmetric rule's stored row (a, b), a < b, is
+        if ((b[m] & 1u) && (v[m] >> (A + F)) == fo.q) {  // a symmetric rule's stored row (a, b), a < b, is
           const unsigned long long mult =                // also the row (b, a) of the file's table
               (fo.sym && ((v[m] >> F) & L.amask) != (rk & L.amask)) ? 2ull : 1ull;
-          atomicAdd(&fh[v[m] & ((1u << F) - 1u)], mult * ((c[m] >> 11) ? 1ull : (1ull | (1ull << 32))));
+          atomicAdd(&fh[v[m] & ((1u << F) - 1u)], mult * ((b[m] >> 11) ? 1ull : (1ull | (1ull << 32))));
         }
     }
   }
   wave_scan_elems<M, false>(b);
-  // (2) at each k-run start: its exclusive X << 10 | position, carried to the k-run's end by one
-  //     max scan (strictly increasing over the starts)
-#pragma unroll
-  for (int m = 0; m < M; ++m) {
-    const uint32_t e = l * M + m;
-    a[m] = ((kst >> m) & 1u) ? (((b[m] - c[m]) << 10) | e) : 0u;
-  }
-  wave_scan_elems<M, true>(a);
-  // (3) at k-run ends: count = its words, S = its files with one word, nf1 = its files;
-  //     count_ge2 = count - S, nf2 = nf1 - S. b = count | count_ge2 << 16, c = nf1 | nf2 << 16
-#pragma unroll
-  for (int m = 0; m < M; ++m) {
-    const uint32_t e = l * M + m;
-    const uint32_t d = b[m] - (a[m] >> 10);
-    const uint32_t nf1 = d & 2047u, s1 = (d >> 11) & 2047u;
-    const uint32_t cnt = e + 1 - (a[m] & 1023u);
-    b[m] = cnt | ((cnt - s1) << 16);
-    c[m] = nf1 | ((nf1 - s1) << 16);
-  }
-  // (4) one output row per k-run end: (key2, count | count_ge2 << 16) staged in this wave's LDS
-  //     rows at its rank among the k-run ends (other elements write a per-lane dummy slot), then
-  //     written out linearly into the task's own word range (coalesced stores on a task-uniform base)
+  // (2) one output row per k-run end, staged in this wave's LDS rows at its rank among the k-run ends (other
+  //     elements write a per-lane dummy slot): key2 and the running totals up to the k-run's end (staged_at).
+  //     No k-run starts are tracked: a row's count and single-word files are the difference to the row before it
   const int type = (int)(rk >> A);
   const int32_t aid = (int32_t)(rk & ((1u << A) - 1u));
   const uint32_t nmine = (uint32_t)__builtin_popcount(kend);
   const uint32_t incl = wave_incl_scan(nmine);
   const uint32_t nout = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-  // the per-rule statistics come from the registers here (only key2 and the counts are staged)
-  const int nq = sR.n_of_type[type];
-  const int r0 = sR.rule_of_type[type][0], r1 = sR.rule_of_type[type][1];
-  // local rules 0 / 1: rows | nf1 << 16, pairs | nf2 << 16 (a symmetric rule's off-diagonal rows twice);
-  // sraw: stored rows | stored pairs << 16
-  uint32_t s0a = 0, s0b = 0, s1a = 0, s1b = 0, sraw = 0, q2 = 0;
-  const uint32_t sym0 = rule_sym(sR, r0) ? 1u : 0u, sym1 = (nq > 1 && rule_sym(sR, r1)) ? 1u : 0u;
   {
     uint32_t idx = incl - nmine;
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       const uint32_t ke = (kend >> m) & 1u;
-      const uint32_t k2 = v[m] >> F, q = k2 >> A, cnt = b[m] & 0xFFFFu, cc = c[m];
+      const uint32_t k2 = v[m] >> F;
       const uint32_t slot = ke ? idx : (uint32_t)(64 * M) + l;
       uint32_t k2s = k2;
       if constexpr (PM) {
         if (pmode) k2s = k2 | (pt[m] << 24);  // the part rides above aid_next (< 2^24 in part mode)
       }
+      const uint32_t e1 = l * M + (uint32_t)(m + 1);
       stgk[slot] = k2s;
-      stgb[slot] = b[m];
+      stgb[slot] = e1 | (b[m] & (2047u << 11)) | ((e1 - (b[m] & 2047u)) << 22);
       idx += ke;
-      if constexpr (!MIRROR) {
-        const uint32_t offd = (k2 & L.amask) != (uint32_t)aid ? 1u : 0u;
-        const uint32_t mult = 1u + (offd & (q == 0 ? sym0 : (q == 1 ? sym1 : 0u)));
-        const uint32_t ra = (1u | ((cc & 0xFFFFu) << 16)) * mult, rb = (cnt | (cc & 0xFFFF0000u)) * mult;
-        sraw += ke ? (1u | (cnt << 16)) : 0u;
-        s0a += (ke && q == 0) ? ra : 0u; s0b += (ke && q == 0) ? rb : 0u;
-        s1a += (ke && q == 1) ? ra : 0u; s1b += (ke && q == 1) ? rb : 0u;
-        q2 |= (ke && q >= 2) ? 1u : 0u;
-      }
-    }
-  }
-  if (!MIRROR && __ballot(q2 != 0u)) {  // more than 2 rules of one type (not in the reference's five)
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-      const uint32_t k2 = v[m] >> F, q = k2 >> A;
-      if (((kend >> m) & 1u) && q >= 2) {
-        const uint32_t cnt = b[m] & 0xFFFFu, cc = c[m];
-        const uint32_t mult = (rule_sym(sR, sR.rule_of_type[type][q]) && (k2 & L.amask) != (uint32_t)aid) ? 2u : 1u;
-        unsigned long long* acc = sacc + sR.rule_of_type[type][q] * 4;
-        atomicAdd(acc + 0, (unsigned long long)mult); atomicAdd(acc + 1, (unsigned long long)cnt * mult);
-        atomicAdd(acc + 2, (unsigned long long)(cc & 0xFFFFu) * mult);
-        atomicAdd(acc + 3, (unsigned long long)(cc >> 16) * mult);
-      }
     }
   }
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  // (3) the rows are written out linearly into the task's own word range (coalesced stores on a task-uniform
+  //     base). The per-rule statistics are differences of the staged totals at row ranks: the local rule is
+  //     key2's top field, so rule q's rows are the ranks [rows below q << A, rows below (q + 1) << A), and a
+  //     symmetric rule's diagonal (aid_next == aid; its off-diagonal rows count twice: 2 * total - diagonal) is
+  //     the ranks of one key2. The ranks come from one compare per 64 rows and boundary, nothing per element.
+  const int nq = sR.n_of_type[type];
+  const int r0 = sR.rule_of_type[type][0], r1 = sR.rule_of_type[type][1];
+  const bool sym0 = !MIRROR && rule_sym(sR, r0), sym1 = !MIRROR && nq > 1 && rule_sym(sR, r1);
+  const uint32_t kmask = pmode ? 0xFFFFFFu : ~0u;
+  const uint32_t q1 = 1u << A, kd0 = (uint32_t)aid, kd1 = q1 | (uint32_t)aid;
+  uint32_t n1 = 0, n2 = 0, d0a = 0, d0b = 0, d1a = 0, d1b = 0;  // rows below: q = 1, q = 2, the diagonals' ranges
   const bool store = O.cap != 0;
   const uint64_t ob = obegin + (MIRROR ? fo.mirror_off : 0ull);
   uint8_t* o_rule = O.rule + ob;
@@ -1925,10 +1913,26 @@ __device__ __forceinline__ uint32_t fold_pass(const uint32_t (&v)[M], uint32_t p
   int32_t* o_next = O.aid_next + ob;
   uint32_t* o_cnt = O.count + ob;
   uint32_t* o_c2 = O.count_ge2 + ob;
-  if (store)
-    for (uint32_t i = l; i < nout; i += 64) {
-      const uint32_t k2 = stgk[i], bb = stgb[i];
-      const uint32_t q = k2 >> A;
+  for (uint32_t base = 0; base < nout; base += 64) {
+    const uint32_t i = base + l;
+    const bool in = i < nout;
+    const uint32_t k2 = stgk[i];  // i < 64 * M: inside the staging row (stale past nout, unused)
+    if constexpr (!MIRROR) {
+      const uint32_t key = in ? (k2 & kmask) : ~0u;
+      n1 += (uint32_t)__popcll(__ballot(key < q1));
+      if (nq > 1) n2 += (uint32_t)__popcll(__ballot(key < 2u * q1));
+      if (sym0) {
+        d0a += (uint32_t)__popcll(__ballot(key < kd0));
+        d0b += (uint32_t)__popcll(__ballot(key <= kd0));
+      }
+      if (sym1) {
+        d1a += (uint32_t)__popcll(__ballot(key < kd1));
+        d1b += (uint32_t)__popcll(__ballot(key <= kd1));
+      }
+    }
+    if (store && in) {
+      const uint32_t bb = staged_counts(stgb, i);
+      const uint32_t q = (k2 & kmask) >> A;
       const int rule = pmode ? (int)(k2 >> 24) : (q == 0 ? r0 : (q == 1 ? r1 : sR.rule_of_type[type][q]));
       const int32_t next = (int32_t)(k2 & L.amask);
       if (MIRROR && next == aid) { o_rule[i] = 0xFF; continue; }  // the diagonal row is its own mirror
@@ -1938,19 +1942,45 @@ __device__ __forceinline__ uint32_t fold_pass(const uint32_t (&v)[M], uint32_t p
       o_cnt[i] = bb & 0xFFFFu;
       o_c2[i] = bb >> 16;
     }
+  }
   if (store)  // the rest of the task's word range holds no row (marked here, no table-wide fill)
     for (uint32_t i = nout + l; i < olen; i += 64) o_rule[i] = 0xFF;
   if constexpr (!MIRROR) {
-    for (int q = 0; q < (nq < 2 ? nq : 2); ++q) {
-      const uint32_t sa = wave_sum(q == 0 ? s0a : s1a), sb = wave_sum(q == 0 ? s0b : s1b);
-      if (l == 0 && sa) {
-        unsigned long long* acc = sacc + (q == 0 ? r0 : r1) * 4;
-        acc[0] += sa & 0xFFFFu; acc[1] += sb & 0xFFFFu; acc[2] += sa >> 16; acc[3] += sb >> 16;
+    if (nq <= 1) n2 = n1;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const uint32_t lo = q == 0 ? 0u : n1, hi = q == 0 ? n1 : n2;
+      if (q < nq && hi > lo) {
+        uint32_t rows = hi - lo;
+        FoldTotals t = staged_range(stgb, lo, hi);
+        if (q == 0 ? sym0 : sym1) {
+          const uint32_t da = q == 0 ? d0a : d1a, db = q == 0 ? d0b : d1b;
+          const FoldTotals dg = staged_range(stgb, da, db);
+          rows += rows - (db - da);
+          t.pairs += t.pairs - dg.pairs; t.files += t.files - dg.files; t.singles += t.singles - dg.singles;
+        }
+        if (l == 0) {
+          unsigned long long* acc = sacc + (q == 0 ? r0 : r1) * 4;
+          acc[0] += rows; acc[1] += t.pairs; acc[2] += t.files; acc[3] += t.files - t.singles;
+        }
       }
     }
     {
-      const uint32_t sr = wave_sum(sraw);
-      if (l == 0) { sacc[STAT_RAW] += sr & 0xFFFFu; sacc[STAT_RAW + 1] += sr >> 16; }
+      const FoldTotals t = staged_range(stgb, 0u, nout);
+      if (l == 0) { sacc[STAT_RAW] += nout; sacc[STAT_RAW + 1] += t.pairs; }
+    }
+    if (nq > 2 && n2 < nout) {  // more than 2 rules of one type (not in the reference's five)
+      for (uint32_t i = n2 + l; i < nout; i += 64) {
+        const uint32_t k2 = stgk[i] & kmask, q = k2 >> A;
+        if ((int)q >= nq) continue;
+        const uint32_t d = stgb[i] - staged_at(stgb, i);
+        const uint32_t cnt = d & 2047u, s1 = (d >> 11) & 2047u, nf1 = cnt - (d >> 22);
+        const uint32_t mult = (rule_sym(sR, sR.rule_of_type[type][q]) && (k2 & L.amask) != (uint32_t)aid) ? 2u : 1u;
+        unsigned long long* acc = sacc + sR.rule_of_type[type][q] * 4;
+        atomicAdd(acc + 0, (unsigned long long)mult); atomicAdd(acc + 1, (unsigned long long)cnt * mult);
+        atomicAdd(acc + 2, (unsigned long long)nf1 * mult);
+        atomicAdd(acc + 3, (unsigned long long)(nf1 - s1) * mult);
+      }
     }
   }
   __builtin_amdgcn_wave_barrier();  // the staging rows are rewritten by the next pass / task
@@ -1980,18 +2010,17 @@ __device__ __forceinline__ void agg_fold(uint32_t (&v)[M], uint64_t obegin, uint
   // part mode: parts of the elements and of the cross-lane neighbours (words of one key are in file
   // order, and the part is non-decreasing in the file for a fixed key, so a part's words stay adjacent)
   uint32_t pt[PM ? M : 1];
-  uint32_t ppl = 0, pnl = 0;
+  uint32_t pnl = 0;
   const bool pmode = PM && fo.parts;
   if constexpr (PM) {
     if (pmode) {
 #pragma unroll
       for (int m = 0; m < M; ++m) pt[m] = v[m] != W_EMPTY ? word_part(*P, v[m], rk & L.amask, L) : 0xFFu;
-      ppl = lane_prev(pt[M - 1]);
       pnl = lane_next(pt[0]);
     }
   }
   const uint32_t nout =
-      fold_pass<M, FO, PM, false>(v, pl, nl, pt, ppl, pnl, pmode, obegin, olen, rk, sR, L, O, fo, fh, stgk, stgb, sacc);
+      fold_pass<M, FO, PM, false>(v, pl, nl, pt, pnl, pmode, obegin, olen, rk, sR, L, O, fo, fh, stgk, stgb, sacc);
   if constexpr (PM && MIR) {
     if (pmode && fo.mirror_off) {
       // the mirrors' parts differ from the rows' only for words of a cut file between the two keys
@@ -2002,10 +2031,9 @@ __device__ __forceinline__ void agg_fold(uint32_t (&v)[M], uint64_t obegin, uint
         differ |= pm != pt[m];
         pt[m] = pm;
       }
-      ppl = lane_prev(pt[M - 1]);
       pnl = lane_next(pt[0]);
       if (__ballot(differ)) {
-        fold_pass<M, FO, PM, true>(v, pl, nl, pt, ppl, pnl, pmode, obegin, olen, rk, sR, L, O, fo, fh, stgk, stgb,
+        fold_pass<M, FO, PM, true>(v, pl, nl, pt, pnl, pmode, obegin, olen, rk, sR, L, O, fo, fh, stgk, stgb,
                                    sacc);
       } else {  // the same runs: the staged rows with (aid, aid_next) swapped
         const int32_t aid = (int32_t)(rk & L.amask);
@@ -2018,8 +2046,9 @@ __device__ __forceinline__ void agg_fold(uint32_t (&v)[M], uint64_t obegin, uint
             O.rule[ob + i] = (uint8_t)(k2 >> 24);
             O.aid[ob + i] = next;
             O.aid_next[ob + i] = aid;
-            O.count[ob + i] = stgb[i] & 0xFFFFu;
-            O.count_ge2[ob + i] = stgb[i] >> 16;
+            const uint32_t bb = staged_counts(stgb, i);
+            O.count[ob + i] = bb & 0xFFFFu;
+            O.count_ge2[ob + i] = bb >> 16;
           }
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -2029,13 +2058,13 @@ __device__ __forceinline__ void agg_fold(uint32_t (&v)[M], uint64_t obegin, uint
 }
 
 // One wave per task of <= 64*M words (rows and split buckets): bitonic sort in registers, then
-// run-length folding with prefix / max scans only (no LDS, no atomics on the data path).
+// run-length folding with one prefix scan (no atomics on the data path).
 //   w-runs (equal words = one (rule, aid_next, file)): per-file count cf
 //   k-runs (equal rule|aid_next): count = sum cf, count_ge2 = sum of cf >= 2,
 //                                 nf1 = w-runs, nf2 = w-runs with cf >= 2
 // The next task's words are loaded while the current one is folded. Per-rule statistics go
-// through a per-wave LDS accumulator (one lane, after wave sums of packed 16-bit fields: a
-// task holds <= 1024 words), so no per-thread accumulator arrays take registers.
+// through a per-wave LDS accumulator (one lane, from differences of the staged running totals:
+// fold_pass), so no per-thread accumulators take registers.
 // FOM: 0 no FileOpts; 1 FileOpts with key cuts / part mode (static per-file table of FO_MAXF rows + the part
 // tables in LDS); 3 part mode with the explicit mirror rows (ottohip_table_count_parts); 2 per-file rows only (the histogram of the call's fo.nf files in dynamic LDS, fo.nf * 8 bytes:
 // the main build's statistics cost no occupancy)
@@ -2050,7 +2079,7 @@ __global__ __launch_bounds__(256, (M >= 16 ? (FOM == 1 ? 2 : (FOM == 3 ? 1 : 4))
   constexpr bool FO = FOM != 0;
   __shared__ unsigned long long sacc[4][STAT_STRIDE];
   __shared__ RulesDev sR;
-  __shared__ uint32_t stg[4][2][64 * M + 64];  // per wave: output rows of one task (key2, count | count_ge2 << 16),
+  __shared__ uint32_t stg[4][2][64 * M + 64];  // per wave: output rows of one task (key2, running totals: staged_at),
                                               // + one dummy slot per lane
   constexpr bool PMODE = FOM == 1 || FOM == 3;
   __shared__ unsigned long long fh_s[PMODE ? FO_MAXF : 1];  // per-file rows of the FileOpts rule
