@@ -561,8 +561,12 @@ static int covis_emit_words(ottohip_ctx* ctx, const Front& F, const ottohip_even
   const bool tasks = !(getenv("OTTOHIP_EMIT_TASKS") && !strcmp(getenv("OTTOHIP_EMIT_TASKS"), "0"));
   // two pairs per lane per flush round (OTTOHIP_EMIT_FLUSH2=0: one; read per call)
   const bool fl2 = !(getenv("OTTOHIP_EMIT_FLUSH2") && !strcmp(getenv("OTTOHIP_EMIT_FLUSH2"), "0"));
-  auto ek = guard ? (tasks ? k_emit<true, true, true> : k_emit<true, false, true>)
-                  : (tasks ? (fl2 ? k_emit<false, true, true> : k_emit<false, true, false>) : k_emit<false, false, true>);
+  // groups of EB_Q partners per lane in the flush (OTTOHIP_EMIT_FLUSHQ=0: emit_flush2, for A/B runs; read per call);
+  // it needs the task lists, and OTTOHIP_EMIT_FLUSH2=0 still selects the one-pair flush
+  const bool flq = tasks && fl2 && !(getenv("OTTOHIP_EMIT_FLUSHQ") && !strcmp(getenv("OTTOHIP_EMIT_FLUSHQ"), "0"));
+  auto ek = guard ? (tasks ? (flq ? k_emit<true, true, true, EB_Q> : k_emit<true, true, true>) : k_emit<true, false, true>)
+                  : (tasks ? (flq ? k_emit<false, true, true, EB_Q> : fl2 ? k_emit<false, true, true> : k_emit<false, true, false>)
+                           : k_emit<false, false, true>);
   if (F.NB > 0)
     ek<<<(unsigned)F.NB, 64, 0, s>>>(F.off, F.first, F.NB, F.evp, F.R, F.Lt, F.fb, ev->n_files, F.fid, F.cnt,
                                          EvOff{F.poff, F.poff32, nullptr}, w0, eerr, dbg);

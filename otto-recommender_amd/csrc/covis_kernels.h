@@ -1131,7 +1131,9 @@ __device__ __forceinline__ void emit_session(const SessView& S, int64_t e0, cons
 //           (flattened start, list position, exclusion, output address); the wave then expands
 //           the records 64 pairs at a time: each lane finds its record by binary search and
 //           writes one word. Every lane writes a word in every round but the last of a flush,
-//           independent of session length or of how selective a rule's type mask is.
+//           independent of session length or of how selective a rule's type mask is. (The default
+//           flush, emit_flushq, expands 64 groups of four consecutive partners of one record at a
+//           time: a lane finds its record once per group.)
 // Sessions of more than LCAP events take k_emit_long.
 constexpr int EB_CAP = 512;    // events per batch (positions fit 10 bits)
 #ifndef OH_EB_RCAP
@@ -1147,10 +1149,10 @@ static_assert(EB_RCAP >= 64 && EB_RCAP <= 128, "records per emit flush");
 constexpr uint32_t EB_NONE = 1023u;
 
 struct EmitRecs {
-  uint4 rec[EB_RCAP];                   // per record: start, list position | exclusion, word high bits,
-                                        // smallest partner aid written (symmetric rules: the event's aid)
+  uint4 rec[EB_RCAP];                   // per record: start (emit_flushq: partner count), list position | exclusion,
+                                        // word high bits, smallest partner aid written (symmetric rules: the event's aid)
   uint64_t rout[EB_RCAP];
-  uint32_t rpre[EB_RCAP];               // record start in the flattened pair order
+  uint32_t rpre[EB_RCAP];               // record start in the flattened pair order (emit_flushq: in groups of Q partners)
 };
 struct EmitPre {
   uint16_t pst[3][64], pen[3][64];      // per-type prefix counts at session start / end
@@ -1311,6 +1313,125 @@ __device__ __forceinline__ void emit_flush2(EmitLds& S, int nrec, uint32_t tot, 
 #endif
 }
 
+// A flush whose unit is a group of Q consecutive partners of one record: lane k of a round takes group c + k, so
+// the mark protocol above (one 64-group window per round), the record lookup, the exclusion fields and the output
+// address are paid once per Q partners. Pass 3 builds the records for it: rpre = the record's start in groups
+// (a record of len partners holds ceil(len / Q) groups, the last one padded), rec.x = len, tot counts groups.
+// Rank of a lane's first written word in its record's output: the spanning record's carry (wave-uniform, as above)
+// plus the exclusive wave scan of the per-lane written counts minus that scan at the record's first lane of the
+// round. Inside a run the words land in partner order, as from the other flushes.
+// OH_EMIT_WIDE: a lane's written words are moved to the front of its registers and leave in one store of their
+// count (dword .. dwordx4, dword aligned); else one dword store per partner slot.
+#ifndef OH_EMIT_Q
+#define OH_EMIT_Q 4
+#endif
+#ifndef OH_EMIT_WIDE
+#define OH_EMIT_WIDE 1
+#endif
+constexpr int EB_Q = OH_EMIT_Q;  // partners per lane and round of emit_flushq
+static_assert(EB_Q == 2 || EB_Q == 4 || EB_Q == 8, "partners per lane of the emit flush");
+typedef uint32_t emit_w2 __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t emit_w3 __attribute__((ext_vector_type(3), aligned(4)));
+typedef uint32_t emit_w4 __attribute__((ext_vector_type(4), aligned(4)));
+
+// words w[0, n) of a lane to p[0, n), n <= 4, in one store
+__device__ __forceinline__ void emit_store_n(uint32_t* __restrict__ p, const uint32_t* w, uint32_t n) {
+  if (n == 4) *(emit_w4*)p = emit_w4{w[0], w[1], w[2], w[3]};
+  else if (n == 3) *(emit_w3*)p = emit_w3{w[0], w[1], w[2]};
+  else if (n == 2) *(emit_w2*)p = emit_w2{w[0], w[1]};
+  else if (n == 1) *p = w[0];
+}
+
+template <int Q, bool GUARD>
+__device__ __forceinline__ void emit_flushq(EmitLds& S, int nrec, uint32_t tot, int F, uint32_t* __restrict__ words,
+                                            int dbg, uint32_t& rid, int* __restrict__ err) {
+  if (dbg & 2) return;  // profiling ablation: records are built, never expanded
+  const uint32_t l = lane_id();
+  const uint32_t sa = (int)l < nrec ? S.u.r.rpre[l] : 0xFFFFFFFFu;
+  const uint32_t sb = (int)l + 64 < nrec ? S.u.r.rpre[l + 64] : 0xFFFFFFFFu;
+  const uint64_t upto = (2ull << l) - 1ull;  // lanes <= l
+  int ob = -1;        // last record starting before the round's window
+  uint32_t cc = 0;    // words written in earlier rounds by the record spanning into this round
+  for (uint32_t c = 0; c < tot; c += 64) {
+    ++rid;
+    if (sa - c < 64u) S.mark[sa - c] = rid;
+    if (sb - c < 64u) S.mark[sb - c] = rid;
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const uint64_t mm = __ballot(S.mark[l] == rid);
+    const uint64_t mle = mm & upto;
+    const int oraw = ob + (int)__popcll(mle);
+#ifndef OH_EMIT_NOCHECK  // always on, as in emit_flush2: the record index clamped into [0, nrec), marks counted below
+    const int o = min(max(oraw, 0), nrec - 1);
+#else
+    const int o = oraw;
+#endif
+    ob += (int)__popcll(mm);
+    const uint32_t g = c + l;
+    const bool bad = GUARD && g < tot && (oraw < 0 || oraw >= nrec);
+    if (bad) atomicOr(err, 8);
+    uint32_t w[Q];
+    bool q[Q];
+#pragma unroll
+    for (int k = 0; k < Q; ++k) { w[k] = 0; q[k] = false; }
+    uint64_t d = 0;
+    uint32_t first = 0;  // the record's first lane in this round (lane 0 for the record spanning into it)
+    if (g < tot && !bad) {
+      const uint4 rc = S.u.r.rec[o];
+      const uint32_t st = S.u.r.rpre[o];
+      first = st > c ? st - c : 0u;
+      const uint32_t k0 = (g - st) * (uint32_t)Q;
+      const uint32_t jb = (rc.y & 1023u) + k0, xlo = (rc.y >> 10) & 1023u, xlen = rc.y >> 21;
+      const uint32_t nv = rc.x - k0;  // partners from this group on (>= 1; the record's last group is padded to Q)
+#pragma unroll
+      for (int k = 0; k < Q; ++k) {   // the Q list reads in flight together: a padding slot reads a clamped position
+        uint32_t j = jb + (uint32_t)k;
+        if (j >= xlo) j += xlen;
+        const uint32_t a = (uint32_t)ev_aid(S.tev[min(j, (uint32_t)EB_CAP - 1u)]);
+        q[k] = (uint32_t)k < nv && a >= rc.w;
+        w[k] = rc.z | (a << F);
+      }
+      d = S.u.r.rout[o];
+    }
+    uint32_t n = 0;
+#pragma unroll
+    for (int k = 0; k < Q; ++k) n += q[k] ? 1u : 0u;
+    const uint32_t ex = wave_incl_scan(n) - n;
+    const uint32_t car = mle ? 0u : cc;
+    const uint32_t rank = car + ex - (uint32_t)__shfl((int)ex, (int)first);
+    cc = (uint32_t)__builtin_amdgcn_readlane((int)(rank + n), 63);
+    if (!(dbg & 1)) {
+      uint32_t* __restrict__ p = words + (d + rank);
+#if OH_EMIT_WIDE
+      // written words to the front, in order: from the top, a hole takes the (already packed) words above it
+#pragma unroll
+      for (int k = Q - 2; k >= 0; --k)
+        if (!q[k]) {
+#pragma unroll
+          for (int i = k; i < Q - 1; ++i) w[i] = w[i + 1];
+        }
+      if constexpr (Q <= 4) {
+        emit_store_n(p, w, n);
+      } else {
+        emit_store_n(p, w, min(n, 4u));
+        if (n > 4u) emit_store_n(p + 4, w + 4, n - 4u);
+      }
+#else
+      uint32_t pk = 0;
+#pragma unroll
+      for (int k = 0; k < Q; ++k) {
+        if (q[k]) p[pk] = w[k];
+        pk += q[k] ? 1u : 0u;
+      }
+#endif
+    }
+  }
+  // every record start falls in exactly one round: the marks seen must number nrec (err bit 8 -> the call fails)
+#ifndef OH_EMIT_NOCHECK
+  if (tot > 0 && ob != nrec - 1 && l == 0) atomicOr(err, 8);
+#endif
+}
+
 // Per event type, the (rule, next type) windows an event of that type writes, as pass 3's task list: entry
 // q | tt << 4 | sym << 6, the non-symmetric rules first (a symmetric record's written length is only known to
 // S2's count, so it goes last in the event's run)
@@ -1335,13 +1456,23 @@ __device__ inline void emit_tasks_build(const RulesDev& R, EmitTasks& T) {
 
 // GUARD (OTTOHIP_DEBUG): bounds checks of the record arrays (err bit 8). TASKS: pass 3 iterates the per-type
 // task lists (lanes of different types search their own lists together); else (OTTOHIP_EMIT_TASKS=0) every
-// (rule, next type) of the wave's types in turn
-template <bool GUARD, bool TASKS, bool FL2 = true>
+// (rule, next type) of the wave's types in turn. FQ > 0: groups of FQ partners per lane (emit_flushq; pass 3 builds its
+// records in groups and skips a symmetric record that writes nothing); FQ == 0: FL2 picks emit_flush2 / emit_flush
+template <bool GUARD, bool FL2, int FQ>
+__device__ __forceinline__ void emit_flush_sel(EmitLds& S, int nrec, uint32_t tot, int F, uint32_t* __restrict__ words,
+                                               int dbg, uint32_t& rid, int* __restrict__ err) {
+  if constexpr (FQ > 0) emit_flushq<FQ, GUARD>(S, nrec, tot, F, words, dbg, rid, err);
+  else if constexpr (FL2) emit_flush2<GUARD>(S, nrec, tot, F, words, dbg, rid, err);
+  else emit_flush<GUARD>(S, nrec, tot, F, words, dbg, rid, err);
+}
+
+template <bool GUARD, bool TASKS, bool FL2 = true, int FQ = 0>
 __global__ __launch_bounds__(64) OH_EMIT_WPE void k_emit(const int64_t* __restrict__ off, const int64_t* __restrict__ first,
                                              int64_t NB, const uint64_t* __restrict__ ev, RulesDev R, Layout L,
                                              const int64_t* __restrict__ fb, int nf, const uint32_t* __restrict__ fid,
                                              const uint32_t* __restrict__ cnt, EvOff poff,
                                              uint32_t* __restrict__ words, int* __restrict__ err, int dbg) {
+  static_assert(FQ == 0 || TASKS, "emit_flushq records are built by the task-list pass 3");
   __shared__ EmitLds S;
   __shared__ RulesDev sR;
   __shared__ EmitTasks sT;
@@ -1507,6 +1638,8 @@ __global__ __launch_bounds__(64) OH_EMIT_WPE void k_emit(const int64_t* __restri
             const uint32_t je = (uint32_t)lds_upper_ts(S.tev, own ? (int)rhi : (int)jb, e, tsi + hi);
             len = je - jb;
             if (own) { xlo = rlo; xlen = rhi - rlo; len -= xlen; }
+            // the symmetric record comes last and writes ecnt - eo words: none -> no record, no flush slots
+            if (FQ > 0 && sym && ecnt == eo) len = 0;
           }
           const uint64_t m = __ballot(len > 0);
           const int nn = (int)__popcll(m);
@@ -1514,17 +1647,20 @@ __global__ __launch_bounds__(64) OH_EMIT_WPE void k_emit(const int64_t* __restri
           if (nrec + nn > EB_RCAP) {
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            (FL2 ? emit_flush2<GUARD> : emit_flush<GUARD>)(S, nrec, tot, L.F, words, dbg, rid, err);
+            emit_flush_sel<GUARD, FL2, FQ>(S, nrec, tot, L.F, words, dbg, rid, err);
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             nrec = 0; tot = 0;
           }
-          const uint32_t incl = wave_incl_scan(len);
+          // flattened order: pairs, or groups of FQ partners (a record's last group padded)
+          constexpr uint32_t GQ = FQ > 0 ? (uint32_t)FQ : 1u;
+          const uint32_t units = (len + GQ - 1u) / GQ;
+          const uint32_t incl = wave_incl_scan(units);
           if (GUARD && nrec + nn > EB_RCAP) atomicOr(err, 8);  // the record arrays would overflow
           if (len > 0 && !(GUARD && nrec + (int)mbcnt(m) >= EB_RCAP)) {
             const int ri = nrec + (int)mbcnt(m);
-            S.u.r.rpre[ri] = tot + incl - len;
-            S.u.r.rec[ri] = make_uint4(tot + incl - len, jb | (xlo << 10) | (xlen << 21), ((uint32_t)q << shiftR) | file,
+            S.u.r.rpre[ri] = tot + incl - units;
+            S.u.r.rec[ri] = make_uint4(FQ > 0 ? len : tot + incl - units, jb | (xlo << 10) | (xlen << 21), ((uint32_t)q << shiftR) | file,
                                    sym ? (uint32_t)ev_aid(v) : 0u);
             S.u.r.rout[ri] = eout + eo;
           }
@@ -1564,7 +1700,7 @@ __global__ __launch_bounds__(64) OH_EMIT_WPE void k_emit(const int64_t* __restri
             if (nrec + nn > EB_RCAP) {
               __builtin_amdgcn_wave_barrier();
               __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-              (FL2 ? emit_flush2<GUARD> : emit_flush<GUARD>)(S, nrec, tot, L.F, words, dbg, rid, err);
+              emit_flush_sel<GUARD, FL2, FQ>(S, nrec, tot, L.F, words, dbg, rid, err);
               __builtin_amdgcn_wave_barrier();
               __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
               nrec = 0; tot = 0;
@@ -1589,7 +1725,7 @@ __global__ __launch_bounds__(64) OH_EMIT_WPE void k_emit(const int64_t* __restri
     if (nrec > 0) {
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      (FL2 ? emit_flush2<GUARD> : emit_flush<GUARD>)(S, nrec, tot, L.F, words, dbg, rid, err);
+      emit_flush_sel<GUARD, FL2, FQ>(S, nrec, tot, L.F, words, dbg, rid, err);
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
