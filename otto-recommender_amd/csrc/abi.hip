@@ -924,12 +924,29 @@ static int covis_reduce(ottohip_ctx* ctx, uint32_t* w0, uint32_t* w1, uint64_t P
     k_split_hist<<<(unsigned)nchunks, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, wcur0, w1, Lt.F, hmat);
     if ((rc = exclusive_scan_u32(ctx, hmat, hoff, nent, hoff + nent, s))) return rc;
     static const int sub = getenv("OTTOHIP_SPLIT_SUB") ? atoi(getenv("OTTOHIP_SPLIT_SUB")) : 4096;  // A/B switch
+    // OTTOHIP_SPLIT_LDS (read per call; 0: off): chunks of >= OTTOHIP_SPLIT_LDS_MIN words (default SPLIT_LDS_MIN) are
+    // scattered by k_split_scatter_lds, a whole chunk staged in LDS; the shorter ones by k_split_scatter as before.
+    // Both kernels run over the same chunks and each leaves the other's at once.
+    const char* lds_env = getenv("OTTOHIP_SPLIT_LDS");
+    const bool split_lds = lds_env ? atoi(lds_env) != 0 : SPLIT_LDS_DEFAULT;
+    const char* ldsmin_env = getenv("OTTOHIP_SPLIT_LDS_MIN");
+    const uint32_t lds_min = (uint32_t)std::min(SPLIT_CH + 1, std::max(0, ldsmin_env ? atoi(ldsmin_env) : SPLIT_LDS_MIN));
+    const int lds_t = getenv("OTTOHIP_SPLIT_LDS_T") ? atoi(getenv("OTTOHIP_SPLIT_LDS_T")) : SPLIT_LT;  // A/B switch
     auto scatter = [&](uint32_t c0, uint32_t c1) {
       if (c1 <= c0) return;
+      uint32_t max_len = SPLIT_CH;
+      if (split_lds) {
+        if (lds_t == 512)
+          k_split_scatter_lds<512><<<c1 - c0, 512, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, lds_min);
+        else
+          k_split_scatter_lds<SPLIT_LT><<<c1 - c0, SPLIT_LT, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, lds_min);
+        if (lds_min <= 1) return;  // (no chunk is empty)
+        max_len = lds_min - 1;
+      }
       if (sub == 8192)
-        k_split_scatter<8192><<<c1 - c0, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0);
+        k_split_scatter<8192><<<c1 - c0, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, max_len);
       else
-        k_split_scatter<4096><<<c1 - c0, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0);
+        k_split_scatter<4096><<<c1 - c0, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, max_len);
     };
     scatter(0, cA);
     // next lists (a sub-bucket is one task in exactly one list: ndig bounds every list): the other

@@ -2752,6 +2752,9 @@ __global__ __launch_bounds__(SPLIT_T) void k_split_hist(const Task* __restrict__
 }
 
 // SUB: scatter sub-tile (staged in LDS in digit order); SUB / SPLIT_T words per thread in registers
+#ifndef OH_SPLIT_ONE
+#define OH_SPLIT_ONE 1  // -DOH_SPLIT_ONE=0: a one-chunk task of one sub-tile is counted in a pass of its own, as the longer ones
+#endif
 template <int SUB>
 __global__ __launch_bounds__(SPLIT_T) void k_split_scatter(const Task* __restrict__ tasks, int64_t n,
                                                            const uint64_t* __restrict__ chunk_base,
@@ -2759,8 +2762,10 @@ __global__ __launch_bounds__(SPLIT_T) void k_split_scatter(const Task* __restric
                                                            const uint64_t* __restrict__ mat_base,
                                                            const uint64_t* __restrict__ hoff,
                                                            uint32_t* __restrict__ w0, uint32_t* __restrict__ w1, int F,
-                                                           uint32_t* __restrict__ hmat, uint32_t chunk0 = 0) {
+                                                           uint32_t* __restrict__ hmat, uint32_t chunk0 = 0,
+                                                           uint32_t max_len = SPLIT_CH) {
   // chunk0: the first chunk of this launch (a split may run as two launches over chunk ranges)
+  // max_len: chunks of more words are left to k_split_scatter_lds (launched over the same chunks)
   constexpr int DPT = SPLIT_DMAX / SPLIT_T;  // digits per thread in the scans
   __shared__ uint32_t h[SPLIT_DMAX], st[SPLIT_DMAX];
   __shared__ uint64_t gb[SPLIT_DMAX];
@@ -2773,12 +2778,17 @@ __global__ __launch_bounds__(SPLIT_T) void k_split_scatter(const Task* __restric
   const uint32_t c = (uint32_t)(cid - chunk_base[t]);
   const uint64_t c0 = (uint64_t)c * SPLIT_CH;
   const uint64_t c1 = c0 + SPLIT_CH < T.len ? c0 + SPLIT_CH : T.len;
+  if (c1 - c0 > (uint64_t)max_len) return;  // (block-uniform, before the first barrier)
   const uint32_t* Win = (T.buf ? w1 : w0) + T.begin;
   uint32_t* Wout = T.buf ? w0 : w1;
   constexpr int SUB_PER_T = SUB / SPLIT_T;
   const int tid = threadIdx.x;
   const uint64_t mb = mat_base[t];
-  if (nch == 1 && c_split_fuse) {
+  // a one-chunk task of one sub-tile: the sub-tile's histogram below is the task's, so there is no count pass;
+  // its scan gives the bucket starts and the counts of hmat
+  const bool one = OH_SPLIT_ONE && nch == 1 && c_split_fuse && c1 <= (uint64_t)SUB;
+  if (one) {  // (gb is set by the sub-tile's scan)
+  } else if (nch == 1 && c_split_fuse) {
     // one-chunk task (<= SPLIT_CH words): its digit counts come from this block (the words are read
     // twice here, the second time from the caches, instead of once by k_split_hist and once here from
     // HBM); they go to hmat for k_split_classify, and the bucket starts are a scan of them
@@ -2857,6 +2867,7 @@ __global__ __launch_bounds__(SPLIT_T) void k_split_scatter(const Task* __restric
 #pragma unroll
       for (int q = 0; q < DPT; ++q) {
         st[tid * DPT + q] = run;
+        if (one && (uint32_t)(tid * DPT + q) < nd) { gb[tid * DPT + q] = T.begin + run; hmat[mb + tid * DPT + q] = v[q]; }
         run += v[q];
       }
     }
@@ -2868,10 +2879,117 @@ __global__ __launch_bounds__(SPLIT_T) void k_split_scatter(const Task* __restric
     for (int p = tid; p < m; p += SPLIT_T) {
       const uint32_t w = stage[p];
       const uint32_t d = split_digit(w, F, T.rem, nd);
+#if defined(OH_SPLIT_ABL) && OH_SPLIT_ABL == 1
+      // timing ablation: linear stores at the chunk's own place (inside the task's range; wrong buckets). The
+      // never-true compare keeps the digit hash and the cursor loads in the code.
+      Wout[T.begin + s0 + p + (gb[d] + (p - st[d]) == ~0ull ? 1u : 0u)] = w;
+#else
       Wout[gb[d] + (p - st[d])] = w;
+#endif
     }
     __syncthreads();
     for (uint32_t d = tid; d < nd; d += SPLIT_T) gb[d] += h[d];  // this chunk's cursor per digit moves past the sub-tile
+  }
+}
+
+// The scatter with a whole chunk staged in LDS: one workgroup per chunk (grid and chunk -> task map of
+// k_split_scatter). The chunk's digit counts (hmat, or counted here for a one-chunk task) are scanned once
+// into per-digit LDS cursors; every word then takes its staging slot by one returning LDS atomic on its
+// digit's cursor and goes straight to stage[], so no word, digit or rank is held in registers across a
+// barrier. After one barrier the chunk leaves in digit order: consecutive lanes write consecutive words, and
+// a digit's run is the chunk's whole share of it (len / nd >= 32 words for a full chunk) instead of a
+// 4096-word sub-tile's. The zeroing, the 512-digit scan and the barriers are paid once per chunk.
+// delta[d] = the digit's global cursor minus its local start (64 bits, wraps), so position p goes to
+// delta[digit] + p. LDS: 64 KB stage + 6 KB tables, two workgroups per CU.
+// min_len: chunks of fewer words are left to k_split_scatter<4096> (launched over the same chunks).
+constexpr int SPLIT_LT = 1024;  // threads per workgroup (OTTOHIP_SPLIT_LDS_T=512: level-0 launch 4.8 vs 4.3 ms)
+// OTTOHIP_SPLIT_LDS; off: measured no faster than k_split_scatter<4096> (reduce 23.1 vs 22.6 ms same box)
+constexpr bool SPLIT_LDS_DEFAULT = false;
+constexpr int SPLIT_LDS_MIN = 4097;  // OTTOHIP_SPLIT_LDS_MIN: a chunk of <= 4096 words is one sub-tile of k_split_scatter
+template <int TB>
+__global__ __launch_bounds__(TB) void k_split_scatter_lds(const Task* __restrict__ tasks, int64_t n,
+                                                          const uint64_t* __restrict__ chunk_base,
+                                                          const uint32_t* __restrict__ chunk_task,
+                                                          const uint64_t* __restrict__ mat_base,
+                                                          const uint64_t* __restrict__ hoff,
+                                                          uint32_t* __restrict__ w0, uint32_t* __restrict__ w1,
+                                                          int F, uint32_t* __restrict__ hmat, uint32_t chunk0,
+                                                          uint32_t min_len) {
+  static_assert(TB >= SPLIT_DMAX, "one digit per thread in the scan");
+  __shared__ uint32_t stage[SPLIT_CH];
+  __shared__ uint32_t cur[SPLIT_DMAX];
+  __shared__ uint64_t delta[SPLIT_DMAX];
+  __shared__ uint32_t wsum[TB / 64];
+  const uint32_t cid = chunk0 + blockIdx.x;
+  const int64_t t = chunk_task[cid];
+  const Task T = tasks[t];
+  const uint32_t nd = split_ndig(T), nch = (uint32_t)ceil_div((int64_t)T.len, SPLIT_CH);
+  const uint32_t c = (uint32_t)(cid - chunk_base[t]);
+  const uint64_t c0 = (uint64_t)c * SPLIT_CH;
+  const uint64_t c1 = c0 + SPLIT_CH < T.len ? c0 + SPLIT_CH : T.len;
+  const uint32_t m = (uint32_t)(c1 - c0);
+  if (m < min_len) return;  // (block-uniform, before the first barrier)
+  const uint32_t* Win = (T.buf ? w1 : w0) + T.begin + c0;
+  uint32_t* Wout = T.buf ? w0 : w1;
+  const uint32_t tid = threadIdx.x;
+  const uint64_t mb = mat_base[t];
+  const bool own = nch == 1 && c_split_fuse;  // one-chunk task: counted here, the counts go to hmat (see k_split_scatter)
+  uint32_t v = 0;
+  uint64_t g = 0;  // the digit's global cursor, unless own
+  if (own) {
+    if (tid < (uint32_t)SPLIT_DMAX) cur[tid] = 0;
+    __syncthreads();
+    for (uint32_t i0 = 0; i0 < m; i0 += 8 * TB) {
+      uint32_t wr[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const uint32_t i = i0 + tid + j * TB;
+        wr[j] = i < m ? Win[i] : 0u;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (c_split_runs) lds_add_runs(cur, split_digit(wr[j], F, T.rem, nd), i0 + tid + j * TB < m);
+        else if (i0 + tid + j * TB < m) atomicAdd(&cur[split_digit(wr[j], F, T.rem, nd)], 1u);
+    }
+    __syncthreads();
+    if (tid < nd) { v = cur[tid]; hmat[mb + tid] = v; }
+  } else if (tid < nd) {
+    const uint64_t e = mb + (uint64_t)tid * nch + c;
+    v = hmat[e];
+    g = T.begin + (hoff[e] - hoff[mb]);
+  }
+  {  // exclusive scan of the chunk's digit counts: the digits' local starts
+    const uint32_t incl = wave_incl_scan(v);
+    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
+    __syncthreads();  // (own: also orders the reads of cur above before the writes below)
+    uint32_t pre = 0;
+    for (uint32_t q = 0; q < (tid >> 6); ++q) pre += wsum[q];
+    const uint32_t st = pre + incl - v;
+    if (own) g = T.begin + st;
+    if (tid < (uint32_t)SPLIT_DMAX) { cur[tid] = st; delta[tid] = g - st; }
+  }
+  __syncthreads();
+  for (uint32_t i0 = 0; i0 < m; i0 += 8 * TB) {  // 8 loads in flight per thread
+    uint32_t wr[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t i = i0 + tid + j * TB;
+      wr[j] = i < m ? Win[i] : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool valid = i0 + tid + j * TB < m;
+      const uint32_t d = split_digit(wr[j], F, T.rem, nd);
+      uint32_t slot;
+      if (c_split_runs) slot = lds_add_runs(cur, d, valid);
+      else slot = valid ? atomicAdd(&cur[d], 1u) : 0u;
+      if (valid && slot < (uint32_t)SPLIT_CH) stage[slot] = wr[j];
+    }
+  }
+  __syncthreads();
+  for (uint32_t p = tid; p < m; p += TB) {
+    const uint32_t w = stage[p];
+    Wout[delta[split_digit(w, F, T.rem, nd)] + p] = w;
   }
 }
 
