@@ -1,7 +1,8 @@
 // Word2Vec top-K neighbour search on gfx950 MFMA (model/w2vec_aids.py:125-173).
 //
 // The reference searches a faiss IVFFlat index (nlist 100, nprobe 3, METRIC_L2) for the first
-// 600k vocabulary rows, k = 20 (w2vec_aids.py:98-110,164). This engine is exact:
+// 600k vocabulary rows, k = 20 (w2vec_aids.py:98-110,164). This engine scans every row: a bf16
+// preselection of KN_C candidates and an exact rerank (states what that guarantees):
 //   1. k_knn_pack: items -> bf16 [V x 128]; columns [0, dim) = v, columns dim, dim+1 = hi/lo
 //      bf16 split of -|v|^2 / 2, rest 0. Queries -> bf16 [Q x 128] with 1, 1 in those columns.
 //      One MFMA product then gives s = q.v - |v|^2/2, and |q - v|^2 = |q|^2 - 2 s ranks like -s.
@@ -87,7 +88,8 @@ constexpr int KN_GL = KN_IT * KN_CH / KN_T;  // glds per thread per tile (8)
 // MODE 2: threshold pre-pass over tiles 0, 16, 32, ... (never the last, partial tile): the
 //   KN_C largest 32-item block maxima of the sampled tiles, a sorted list per query; KN_C
 //   distinct blocks each hold an item scoring >= their maximum, so the KN_C-th of them is a lower
-//   bound of the query's KN_C-th best score -> thr_io[q]. MODE 0 then inserts only items above it.
+//   bound of the query's KN_C-th best score -> thr_io[q] (stored below the lowest key that score can
+//   take). MODE 0 then inserts only items whose key is above it.
 // KS = k-steps of 16 over the packed row: ceil((dim + 2) / 16) rounded up to 7 or 8 (dim 100 -> 7,
 // so the zero padding of columns 112..127 is neither streamed nor multiplied).
 // BUF (MODE 0): the register list keeps scores only (one v_med3 per slot per insert instead of a
@@ -317,7 +319,15 @@ __global__ __launch_bounds__(KN_T) void k_knn_main(const uint4* __restrict__ ite
   if ((ABL == 1 || ABL == 3) && thr == 12345.f) ix[0] = 0;  // keep the ablated scores live
   if (PRE) {  // KN_C distinct blocks hold an item scoring >= their maximum: the KN_C-th largest
               // sampled block maximum is a lower bound of the query's KN_C-th best score
-    if (q < nq) thr_io[q] = nextafterf(sc[KN_C - 1], -INFINITY);  // items tying the bound are still inserted
+    // MODE 0 compares the bound with KEYS, whose 5 low mantissa bits are the row slot: an item scoring
+    // exactly the bound may carry any key of that score's 32-ulp cell, so the bound goes below the cell's
+    // lowest key (low bits 0 for a score >= 0, all ones for a negative one; -inf stays)
+    if (q < nq) {
+      const uint32_t u = __float_as_uint(sc[KN_C - 1]);  // finite or -inf; the next float down, on the bits
+      const uint32_t lo = u & ~31u;
+      const uint32_t t = u == 0xFF800000u ? u : ((u >> 31) ? (u | 31u) + 1u : (lo ? lo - 1u : 0x80000001u));
+      thr_io[q] = __uint_as_float(t);
+    }
     return;
   }
   if constexpr (BUF) {
@@ -457,7 +467,8 @@ void ottohip_knn_index_free(ottohip_knn_index* ix) {
 
 int ottohip_knn_topk(ottohip_ctx* c, const ottohip_knn_index* ix, const int32_t* query_rows, int64_t n_q, int k,
                      int32_t* out_idx, float* out_d2, void* stream) {
-  if (!c || !ix || n_q < 0 || k < 1 || k > KN_KMAX || !out_idx || !out_d2) {
+  // an empty query set has empty outputs, whose device pointers may be null
+  if (!c || !ix || n_q < 0 || k < 1 || k > KN_KMAX || (n_q > 0 && (!out_idx || !out_d2))) {
     set_error("knn_topk: bad arguments (1 <= k <= %d)", KN_KMAX);
     return OTTOHIP_EINVAL;
   }

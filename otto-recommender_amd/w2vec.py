@@ -4,8 +4,11 @@ Mirrors model/w2vec_aids.py:
   load_index_faiss_ivff(embeddings, model_name)                           :98-110
   get_top_k_similar_faiss(words_q, words, map_word_embedding, index, k)   :125-173
   retrieve_w2vec_knns_via_faiss_index(model_name, k, first_n_aids)        :176-206
-The index is exact (bf16 MFMA scores + fp32 rerank, see csrc/knn.hip); the reference's
-faiss IVFFlat (nlist 100, nprobe 3) is approximate. Word2Vec training (gensim) is out of
+The index scans every row (bf16 MFMA scores keep 24 candidates per query, an exact fp32 rerank orders
+them; see csrc/knn.hip): a true neighbour is certain to be returned when fewer than 24 other rows come
+within the bf16 scores' error of it (DESIGN.md §5 kNN states the bound and the envelope in which this is
+an exact search: embeddings centred near the origin, not tightly clustered). The reference's faiss
+IVFFlat (nlist 100, nprobe 3) probes 3 of 100 lists. Word2Vec training (gensim) is out of
 scope: embeddings are an input (a vocabulary `words` in index_to_key order + vectors).
 """
 from __future__ import annotations
@@ -46,8 +49,10 @@ class KnnIndex:
             pass
 
     def search(self, query_rows=None, n_q=None, k: int = 20, stream=None):
-        """k nearest rows per query row in ascending squared L2 (ties by row index):
-        returns torch (idx:int32 [n_q, k], d2:float32 [n_q, k]) on the device."""
+        """k nearest rows per query row in ascending fp32 squared L2, ties by row index: returns torch
+        (idx:int32 [n_q, k], d2:float32 [n_q, k]) on the device; slots past the index size are -1 / inf.
+        The rows are the best k of 24 candidates chosen by bf16 scores (module docstring), so "ties by row
+        index" holds among at most 24 equal-score candidates: of more identical rows, some k come back."""
         import torch
         dev = self.emb.device
         if query_rows is None:
@@ -64,7 +69,7 @@ class KnnIndex:
 
 
 def load_index_faiss_ivff(embeddings, model_name: str | None = None) -> KnnIndex:
-    """w2vec_aids.py:98-110 (the nlist/nprobe of config.W2VEC_MODELS do not apply: exact search)."""
+    """w2vec_aids.py:98-110 (the nlist/nprobe of config.W2VEC_MODELS do not apply: every row is scanned)."""
     return KnnIndex(embeddings)
 
 

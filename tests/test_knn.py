@@ -3,7 +3,9 @@
 Tolerance (floating point): neighbour sets equal to the exact fp32/fp64 search on >= 99.5 %
 of queries (SURVEY.md §8c asks >= 0.99 overlap; the reference's own IVF reached 0.973/0.980),
 squared distances within 1e-5 relative (+1e-6 absolute), dist_w2vec = trunc(d2) within 1,
-rank_w2vec = position 1..k, the query itself first with distance 0."""
+rank_w2vec = position 1..k, the query itself first with distance 0.
+These are friendly inputs; tests/test_knn_edges_gpu.py holds the derived certain-neighbour rule, the pre-pass,
+the index-list rerun, the k-step variants and the shape edges."""
 import numpy as np
 import pytest
 
