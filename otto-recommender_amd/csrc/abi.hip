@@ -664,7 +664,7 @@ static int covis_reduce(ottohip_ctx* ctx, uint32_t* w0, uint32_t* w1, uint64_t P
   }
   unsigned long long *stats, *lcount;
   OH_TRY(ws.get("stats", (size_t)STAT_STRIPES * STAT_STRIDE, &stats));
-  OH_TRY(ws.get("lcount", 8, &lcount));
+  OH_TRY(ws.get("lcount", 2 * LC_WORDS, &lcount));  // two counter sets, by level parity
   hipMemsetAsync(stats, 0, (size_t)STAT_STRIPES * STAT_STRIDE * 8, s);
   hipMemsetAsync(err, 0, sizeof(int), s);
   // rows are written at their task's word offsets; each leaf task marks the rest of its range
@@ -730,7 +730,7 @@ static int covis_reduce(ottohip_ctx* ctx, uint32_t* w0, uint32_t* w1, uint64_t P
   // task lists double-buffered by level parity: level l's sorts (aux stream) may still read theirs
   // while level l + 1's classify fills the other set
   const uint64_t split_extra = P / 512 + 64;
-  auto get_lists = [&](uint64_t capl, const char* split_name, int parity) -> int {
+  auto get_lists = [&](uint64_t capl, const char* split_name, int parity, uint64_t more_split = 0) -> int {
     static const char* names[2][N_SORT] = {{"t_sort0", "t_sort1", "t_sort2", "t_sort3", "t_sort4"},
                                            {"t_sort0b", "t_sort1b", "t_sort2b", "t_sort3b", "t_sort4b"}};
     for (int c = 0; c < N_SORT; ++c)
@@ -738,19 +738,50 @@ static int covis_reduce(ottohip_ctx* ctx, uint32_t* w0, uint32_t* w1, uint64_t P
     if (int r = ws.get(parity ? "t_hashb" : "t_hash", capl * sizeof(Task), reinterpret_cast<void**>(&TL.hash))) return r;
     if (int r = ws.get(parity ? "t_ldsb" : "t_lds", capl * sizeof(Task), reinterpret_cast<void**>(&TL.lds))) return r;
     // the split list also takes the LDS leaf's hot segments (> 512 words each)
-    if (int r = ws.get(split_name, (capl + split_extra) * sizeof(Task), reinterpret_cast<void**>(&TL.split))) return r;
+    // (more_split: room behind the list for the overflow tasks of the hash leaves one level up)
+    if (int r = ws.get(split_name, (capl + split_extra + more_split) * sizeof(Task), reinterpret_cast<void**>(&TL.split))) return r;
     TL.cap = capl;
     return 0;
   };
   if ((rc = get_lists(cap0, "t_splitA", 0))) return rc;
-  hipMemsetAsync(lcount, 0, 8 * 8, s);
-  k_classify_rows<<<grid_for(Rn), 256, 0, s>>>(row_begin, Rn, P, Lt.WB, TL, err, row_base);
   const int agg_grid = ctx->n_cu * 8;
   static const bool overlap = !(getenv("OTTOHIP_REDUCE_OVERLAP") && !strcmp(getenv("OTTOHIP_REDUCE_OVERLAP"), "0"));
   hipStream_t s2 = nullptr;
   if (overlap) {
     OH_TRY(ctx->aux_stream());
     s2 = ctx->aux;
+  }
+  const char* pipe_env = getenv("OTTOHIP_SPLIT_PIPE");
+  const bool pipe_on = pipe_env && atoi(pipe_env) == 1;
+  // The level schedule (OTTOHIP_REDUCE_SCHED=1, read per call; default 0: the loop of blocking reads further
+  // down): a level's hash leaves run on the third stream and their overflow tasks join the next level's split,
+  // the level's split starts at once, and the host reads one counter set per level. Built and measured, off by
+  // default: the split then shares the CUs with the level's register sorts and ends when it did before (DESIGN
+  // §9). The split pipelining, the LDS leaf and the per-task hash profile are written against the other loop and
+  // select it.
+  const char* sched_env = getenv("OTTOHIP_REDUCE_SCHED");
+  const bool sched = s2 != nullptr && sched_env && atoi(sched_env) == 1 && !pipe_on && !lds_leaf &&
+                     getenv("OTTOHIP_HASH_PROF") == nullptr;
+  // the pushers' error flags: with the level schedule a word of the counter set they push to
+  auto level_err = [&](int set) { return sched ? reinterpret_cast<int*>(lcount + set * LC_WORDS + LC_ERR) : err; };
+  hipMemsetAsync(lcount, 0, 2 * LC_WORDS * 8, s);
+  k_classify_rows<<<grid_for(Rn), 256, 0, s>>>(row_begin, Rn, P, Lt.WB, TL, level_err(0), row_base);
+  // Hash leaf grid (OTTOHIP_HASH_GRID, read per call). Unset: as many blocks as are resident at once (two per CU:
+  // 64 KiB of LDS each), which take their tasks from a device counter; n > 0: n blocks, the same; 0: n_cu * 8
+  // blocks that stride over the tasks (three quarters of them wait for a CU slot behind the register sorts).
+  const char* hgrid_env = getenv("OTTOHIP_HASH_GRID");
+  const int hgrid = hgrid_env ? std::max(0, atoi(hgrid_env)) : -1;
+  const int fom = FOhist ? 2 : (FOmir ? 3 : (FOon ? 1 : 0));
+  unsigned int* hnext = nullptr;  // task counters of the hash launches: [0] main / third stream, [1] aux stream
+  if (hgrid != 0) OH_TRY(ws.get("hash_next", 2, &hnext));
+  if (hgrid < 0 && !ctx->hash_resident[fom]) {
+    int nb = 0;
+    hipError_t e = fom == 2   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_agg_hash<2>, AGG_T, 0)
+                   : fom == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_agg_hash<3>, AGG_T, 0)
+                   : fom == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_agg_hash<1>, AGG_T, 0)
+                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_agg_hash<0>, AGG_T, 0);
+    if (e != hipSuccess || nb < 1) { set_error("k_agg_hash<%d>: occupancy query failed", fom); return OTTOHIP_EHIP; }
+    ctx->hash_resident[fom] = nb * ctx->n_cu;
   }
   bool srcA = true;
   bool drained = false;
@@ -762,28 +793,32 @@ static int covis_reduce(ottohip_ctx* ctx, uint32_t* w0, uint32_t* w1, uint64_t P
   // two halves; the next level's leaves of the first half's sub-buckets (hash, then register sorts, on the aux
   // stream) start while the second half is scattered on the main stream. done[c]: tasks of list c of the level
   // whose leaves were launched that way; hash_early: its hash leaves run on the aux stream (ev_hash).
-  const char* pipe_env = getenv("OTTOHIP_SPLIT_PIPE");
-  const bool pipe = s2 != nullptr && !lds_leaf && !dbg && getenv("OTTOHIP_HASH_PROF") == nullptr &&
-                    (pipe_env && atoi(pipe_env) == 1);
+  const bool pipe = s2 != nullptr && !lds_leaf && !dbg && getenv("OTTOHIP_HASH_PROF") == nullptr && pipe_on;
   // splits of >= 2048 chunks (32 M words) are pipelined (OTTOHIP_SPLIT_PIPE_MIN: another bound, for tests)
   const uint64_t PIPE_MIN_CHUNKS = getenv("OTTOHIP_SPLIT_PIPE_MIN") ? (uint64_t)atoll(getenv("OTTOHIP_SPLIT_PIPE_MIN")) : 2048;
   unsigned long long done[N_LISTS] = {};
   bool hash_early = false;
   // leaves of tasks [lo[c], hi[c]) of the sort classes / [lo[N_SORT], hi[N_SORT]) of the hash list, buffer wb0 for
   // buf 0
-  auto launch_hash_range = [&](uint64_t lo, uint64_t hi, uint32_t* wb0, hipStream_t st) {
+  // overflowing tasks go to ov[*n_ov] (capacity: the launch's tasks) and add their split's work to ov_work, if given;
+  // slot: the task counter (launches that can be in flight together take different ones)
+  auto launch_hash_range = [&](uint64_t lo, uint64_t hi, uint32_t* wb0, hipStream_t st, Task* ov,
+                               unsigned long long* n_ov, unsigned long long* ov_work, int slot) {
     if (hi <= lo) return;
     const int64_t nh = (int64_t)(hi - lo);
     const Task* th = TL.hash + lo;
-    const unsigned hg = (unsigned)std::min<int64_t>(nh, (int64_t)agg_grid);
+    const int64_t blocks = hgrid == 0 ? (int64_t)agg_grid : (hgrid > 0 ? (int64_t)hgrid : (int64_t)ctx->hash_resident[fom]);
+    const unsigned hg = (unsigned)std::min<int64_t>(nh, blocks);
+    unsigned int* nt = hgrid == 0 ? nullptr : hnext + slot;
+    if (nt) hipMemsetAsync(nt, 0, sizeof(unsigned int), st);
     if (FOhist)
-      k_agg_hash<2><<<hg, AGG_T, 0, st>>>(th, nh, wb0, w1, row_key, R, Lt, n_rules, O, TL.split, lcount + N_SORT + 1, fo);
+      k_agg_hash<2><<<hg, AGG_T, 0, st>>>(th, nh, wb0, w1, row_key, R, Lt, n_rules, O, ov, n_ov, fo, nt, ov_work);
     else if (FOmir)
-      k_agg_hash<3><<<hg, AGG_T, 0, st>>>(th, nh, wb0, w1, row_key, R, Lt, n_rules, O, TL.split, lcount + N_SORT + 1, fo);
+      k_agg_hash<3><<<hg, AGG_T, 0, st>>>(th, nh, wb0, w1, row_key, R, Lt, n_rules, O, ov, n_ov, fo, nt, ov_work);
     else if (FOon)
-      k_agg_hash<1><<<hg, AGG_T, 0, st>>>(th, nh, wb0, w1, row_key, R, Lt, n_rules, O, TL.split, lcount + N_SORT + 1, fo);
+      k_agg_hash<1><<<hg, AGG_T, 0, st>>>(th, nh, wb0, w1, row_key, R, Lt, n_rules, O, ov, n_ov, fo, nt, ov_work);
     else
-      k_agg_hash<<<hg, AGG_T, 0, st>>>(th, nh, wb0, w1, row_key, R, Lt, n_rules, O, TL.split, lcount + N_SORT + 1, fo);
+      k_agg_hash<<<hg, AGG_T, 0, st>>>(th, nh, wb0, w1, row_key, R, Lt, n_rules, O, ov, n_ov, fo, nt, ov_work);
   };
   auto launch_sorts = [&](const unsigned long long* lo, const unsigned long long* hi, uint32_t* wb0, hipStream_t st) {
     const unsigned sgrid = (unsigned)ctx->n_cu * 32;
@@ -804,7 +839,126 @@ static int covis_reduce(ottohip_ctx* ctx, uint32_t* w0, uint32_t* w1, uint64_t P
     OH_SORT(0, 1) OH_SORT(1, 2) OH_SORT(2, 4) OH_SORT(3, 8) OH_SORT(4, 16)
 #undef OH_SORT
   };
-  for (int level = 0; level < 40; ++level) {
+  static const int sub = getenv("OTTOHIP_SPLIT_SUB") ? atoi(getenv("OTTOHIP_SPLIT_SUB")) : 4096;  // A/B switch
+  // OTTOHIP_SPLIT_LDS (read per call; 0: off): chunks of >= OTTOHIP_SPLIT_LDS_MIN words (default SPLIT_LDS_MIN) are
+  // scattered by k_split_scatter_lds, a whole chunk staged in LDS; the shorter ones by k_split_scatter as before.
+  // Both kernels run over the same chunks and each leaves the other's at once.
+  const char* lds_env = getenv("OTTOHIP_SPLIT_LDS");
+  const bool split_lds = lds_env ? atoi(lds_env) != 0 : SPLIT_LDS_DEFAULT;
+  const char* ldsmin_env = getenv("OTTOHIP_SPLIT_LDS_MIN");
+  const uint32_t lds_min = (uint32_t)std::min(SPLIT_CH + 1, std::max(0, ldsmin_env ? atoi(ldsmin_env) : SPLIT_LDS_MIN));
+  const int lds_t = getenv("OTTOHIP_SPLIT_LDS_T") ? atoi(getenv("OTTOHIP_SPLIT_LDS_T")) : SPLIT_LT;  // A/B switch
+  // chunks [c0, c1) of a level's split, on the main stream
+  auto scatter_chunks = [&](const Task* cur_split, int64_t ns, const uint64_t* chb, const uint32_t* ctask, const uint64_t* mtb,
+                            const uint64_t* hoff, uint32_t* hmat, uint32_t c0, uint32_t c1) {
+    if (c1 <= c0) return;
+    uint32_t max_len = SPLIT_CH;
+    if (split_lds) {
+      if (lds_t == 512)
+        k_split_scatter_lds<512><<<c1 - c0, 512, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, lds_min);
+      else
+        k_split_scatter_lds<SPLIT_LT><<<c1 - c0, SPLIT_LT, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, lds_min);
+      if (lds_min <= 1) return;  // (no chunk is empty)
+      max_len = lds_min - 1;
+    }
+    if (sub == 8192)
+      k_split_scatter<8192><<<c1 - c0, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, max_len);
+    else
+      k_split_scatter<4096><<<c1 - c0, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, max_len);
+  };
+  // The level schedule. Level l's lists and counter set have parity l & 1. At the top of a level the main stream
+  // waits for the hash leaves of the level before (third stream), whose overflow tasks and their split work were
+  // added to this level's set, and the host reads the set once: list counts, the split's chunk / digit / entry
+  // totals (summed by the pushers, so the three scans' totals stay on the device), the overflow count and the
+  // error flags. Then the hash leaves start on the third stream and the register sorts on the aux stream, both
+  // behind ev_fork, and the split of the level's split list plus the deferred overflow tasks runs on the main
+  // stream at once. An overflow task keeps its buf: it is split from the buffer its words are in.
+  // Orderings: the next level's set is zeroed on the main stream before ev_fork, so before this level's classify
+  // and hash leaves, which add to it. A parity's lists are rewritten by the classify two levels on, which waits
+  // for their sorts (ev_join) and, through the next level's top, for their hash leaves (ev_hash).
+  auto sched_levels = [&]() -> int {
+    OH_TRY(ctx->level_buffer());
+    hipStream_t s3 = ctx->aux2;
+    const unsigned long long* hv = ctx->level_host;
+    Task* ovl[2] = {nullptr, nullptr};  // overflow tasks of the hash leaves, by the parity of their level
+    bool hash_pending = false;
+    for (int level = 0; level < 40; ++level) {
+      const int p = level & 1;
+      unsigned long long* C = lcount + p * LC_WORDS;
+      unsigned long long* Cn = lcount + (p ^ 1) * LC_WORDS;
+      wcur0 = (level == 0 || !w2) ? w0 : w2;
+      if (hash_pending) OH_HIP(hipStreamWaitEvent(s, ctx->ev_hash, 0));
+      hash_pending = false;
+      OH_HIP(hipMemcpyAsync(ctx->level_host, C, LC_WORDS * 8, hipMemcpyDeviceToHost, s));
+      OH_HIP(hipMemsetAsync(Cn, 0, LC_WORDS * 8, s));
+      OH_HIP(hipEventRecord(ctx->ev_fork, s));
+      OH_HIP(hipStreamSynchronize(s));  // the level's one host read
+      if (hv[LC_ERR]) {
+        set_error("task list overflow / row too large (err=%d)", (int)hv[LC_ERR]);
+        return OTTOHIP_ELIMIT;
+      }
+      unsigned long long nlist[N_LISTS];
+      for (int c = 0; c < N_LISTS; ++c) nlist[c] = hv[c];
+      const uint64_t nh = nlist[N_SORT], nov = hv[LC_OVERFLOW];
+      const int64_t nsl = (int64_t)nlist[N_SORT + 1], ns = nsl + (int64_t)nov;
+      const int64_t nchunks = (int64_t)hv[LC_CHUNKS], ndig = (int64_t)hv[LC_DIGITS], nent = (int64_t)hv[LC_ENTRIES];
+      if (dbg)
+        fprintf(stderr, "[ottohip] level %d: sort %llu/%llu/%llu/%llu/%llu hash %llu split %llu lds %llu overflow %llu "
+                "(chunks %lld digits %lld entries %lld)\n", level, nlist[0], nlist[1], nlist[2], nlist[3], nlist[4],
+                (unsigned long long)nh, nlist[N_SORT + 1], nlist[N_SORT + 2], (unsigned long long)nov, (long long)nchunks,
+                (long long)ndig, (long long)nent);
+      if ((uint64_t)nsl > TL.cap) { set_error("split list overflow"); return OTTOHIP_ELIMIT; }
+      if (nh) {  // overflowing tasks: to this parity's overflow list, counted and summed in the next level's set
+        if ((rc = ws.get(p ? "t_overB" : "t_overA", (size_t)nh, &ovl[p]))) return rc;
+        OH_HIP(hipStreamWaitEvent(s3, ctx->ev_fork, 0));
+        launch_hash_range(0, nh, wcur0, s3, ovl[p], Cn + LC_OVERFLOW, Cn + LC_CHUNKS, 0);
+        OH_HIP(hipEventRecord(ctx->ev_hash, s3));
+        hash_pending = true;
+      }
+      OH_HIP(hipStreamWaitEvent(s2, ctx->ev_fork, 0));
+      const unsigned long long zero[N_LISTS] = {};
+      launch_sorts(zero, nlist, wcur0, s2);
+      OH_HIP(hipEventRecord(ctx->ev_join[p], s2));
+      if (ns == 0 && !hash_pending) {  // nothing left to split and no overflow to come: both other streams join
+        OH_HIP(hipStreamWaitEvent(s, ctx->ev_join[p], 0));
+        drained = true;
+        return 0;
+      }
+      Task* cur_split = TL.split;
+      uint32_t *nch, *ndg, *nen, *hmat = nullptr;
+      uint64_t *chb, *dgb = nullptr, *mtb = nullptr, *tot2, *hoff = nullptr;
+      if (ns) {
+        // (the list was allocated with room for the overflow of the level before: get_lists(.., nh) below)
+        if (nov)
+          OH_HIP(hipMemcpyAsync(cur_split + nsl, ovl[p ^ 1], (size_t)nov * sizeof(Task), hipMemcpyDeviceToDevice, s));
+        uint32_t* ctask;
+        if ((rc = ws.get("sp_nch", (size_t)ns, &nch)) || (rc = ws.get("sp_ndg", (size_t)ns, &ndg)) ||
+            (rc = ws.get("sp_nen", (size_t)ns, &nen)) || (rc = ws.get("sp_chb", (size_t)ns + 1, &chb)) ||
+            (rc = ws.get("sp_dgb", (size_t)ns + 1, &dgb)) || (rc = ws.get("sp_mtb", (size_t)ns + 1, &mtb)) ||
+            (rc = ws.get("sp_tot", 6, &tot2)) || (rc = ws.get("sp_hmat", (size_t)nent, &hmat)) ||
+            (rc = ws.get("sp_hoff", (size_t)nent + 1, &hoff)) || (rc = ws.get("sp_ctask", (size_t)nchunks, &ctask)))
+          return rc;
+        k_split_prepare<<<grid_for(ns), 256, 0, s>>>(cur_split, ns, nch, ndg, nen);
+        if ((rc = exclusive_scan_u32(ctx, nch, chb, ns, tot2, s)) || (rc = exclusive_scan_u32(ctx, ndg, dgb, ns, tot2 + 1, s)) ||
+            (rc = exclusive_scan_u32(ctx, nen, mtb, ns, tot2 + 2, s)))
+          return rc;
+        k_split_chunk_task<<<grid_for(ns), 256, 0, s>>>(chb, nch, ns, ctask);
+        k_split_hist<<<(unsigned)nchunks, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, wcur0, w1, Lt.F, hmat);
+        if ((rc = exclusive_scan_u32(ctx, hmat, hoff, nent, hoff + nent, s))) return rc;
+        scatter_chunks(cur_split, ns, chb, ctask, mtb, hoff, hmat, 0, (uint32_t)nchunks);
+      }
+      // the next lists: the other parity's set, last read by the sorts (ev_join) and hash leaves (waited for at the
+      // top of this level) of level - 1
+      if (level >= 1) OH_HIP(hipStreamWaitEvent(s, ctx->ev_join[p ^ 1], 0));
+      if ((rc = get_lists(std::max(cap0, (uint64_t)ndig), p ? "t_splitA" : "t_splitB", p ^ 1, nh))) return rc;
+      TL.n = Cn;
+      if (ns) k_split_classify<<<grid_for(ndig), 256, 0, s>>>(cur_split, ns, dgb, mtb, hoff, ndig, TL, level_err(p ^ 1), hmat, 0);
+      if (hipGetLastError() != hipSuccess) { set_error("split launch failed"); return OTTOHIP_EHIP; }
+    }
+    return 0;
+  };
+  if (sched) OH_TRY(sched_levels());
+  for (int level = 0; !sched && level < 40; ++level) {
     wcur0 = (level == 0 || !w2) ? w0 : w2;
     unsigned long long nlist[N_LISTS];
     if ((rc = d2h(nlist, lcount, N_LISTS, s))) return rc;
@@ -842,7 +996,9 @@ static int covis_reduce(ottohip_ctx* ctx, uint32_t* w0, uint32_t* w1, uint64_t P
     // sorts first)
     static const bool hash_first = !(getenv("OTTOHIP_HASH_FIRST") && !strcmp(getenv("OTTOHIP_HASH_FIRST"), "0"));
     const bool hf = hash_first && nlist[N_SORT] > done[N_SORT];
-    auto launch_hash = [&]() { launch_hash_range(done[N_SORT], nlist[N_SORT], wcur0, s); };
+    auto launch_hash = [&]() {
+      launch_hash_range(done[N_SORT], nlist[N_SORT], wcur0, s, TL.split, lcount + N_SORT + 1, nullptr, 0);
+    };
     if (hf) launch_hash();
     launch_sorts(done, nlist, wcur0, ss);
     if (s2) OH_HIP(hipEventRecord(ctx->ev_join[level & 1], s2));
@@ -923,38 +1079,14 @@ static int covis_reduce(ottohip_ctx* ctx, uint32_t* w0, uint32_t* w1, uint64_t P
     k_split_chunk_task<<<grid_for(ns), 256, 0, s>>>(chb, nch, ns, ctask);
     k_split_hist<<<(unsigned)nchunks, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, wcur0, w1, Lt.F, hmat);
     if ((rc = exclusive_scan_u32(ctx, hmat, hoff, nent, hoff + nent, s))) return rc;
-    static const int sub = getenv("OTTOHIP_SPLIT_SUB") ? atoi(getenv("OTTOHIP_SPLIT_SUB")) : 4096;  // A/B switch
-    // OTTOHIP_SPLIT_LDS (read per call; 0: off): chunks of >= OTTOHIP_SPLIT_LDS_MIN words (default SPLIT_LDS_MIN) are
-    // scattered by k_split_scatter_lds, a whole chunk staged in LDS; the shorter ones by k_split_scatter as before.
-    // Both kernels run over the same chunks and each leaves the other's at once.
-    const char* lds_env = getenv("OTTOHIP_SPLIT_LDS");
-    const bool split_lds = lds_env ? atoi(lds_env) != 0 : SPLIT_LDS_DEFAULT;
-    const char* ldsmin_env = getenv("OTTOHIP_SPLIT_LDS_MIN");
-    const uint32_t lds_min = (uint32_t)std::min(SPLIT_CH + 1, std::max(0, ldsmin_env ? atoi(ldsmin_env) : SPLIT_LDS_MIN));
-    const int lds_t = getenv("OTTOHIP_SPLIT_LDS_T") ? atoi(getenv("OTTOHIP_SPLIT_LDS_T")) : SPLIT_LT;  // A/B switch
-    auto scatter = [&](uint32_t c0, uint32_t c1) {
-      if (c1 <= c0) return;
-      uint32_t max_len = SPLIT_CH;
-      if (split_lds) {
-        if (lds_t == 512)
-          k_split_scatter_lds<512><<<c1 - c0, 512, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, lds_min);
-        else
-          k_split_scatter_lds<SPLIT_LT><<<c1 - c0, SPLIT_LT, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, lds_min);
-        if (lds_min <= 1) return;  // (no chunk is empty)
-        max_len = lds_min - 1;
-      }
-      if (sub == 8192)
-        k_split_scatter<8192><<<c1 - c0, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, max_len);
-      else
-        k_split_scatter<4096><<<c1 - c0, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, max_len);
-    };
+    auto scatter = [&](uint32_t c0, uint32_t c1) { scatter_chunks(cur_split, ns, chb, ctask, mtb, hoff, hmat, c0, c1); };
     scatter(0, cA);
     // next lists (a sub-bucket is one task in exactly one list: ndig bounds every list): the other
     // parity's set, last read by the sorts of level - 1
     if (s2 && level >= 1) OH_HIP(hipStreamWaitEvent(s, ctx->ev_join[(level + 1) & 1], 0));
     const uint64_t capn = (uint64_t)ndig;
     if ((rc = get_lists(std::max(cap0, capn), srcA ? "t_splitB" : "t_splitA", (level + 1) & 1))) return rc;
-    hipMemsetAsync(lcount, 0, 8 * 8, s);
+    hipMemsetAsync(lcount, 0, LC_WORDS * 8, s);
     k_split_classify<<<grid_for(dA), 256, 0, s>>>(cur_split, ns, dgb, mtb, hoff, dA, TL, err, hmat, 0);
     if (piped) {
       if (getenv("OTTOHIP_SPLIT_PIPE_LOG")) fprintf(stderr, "[ottohip] level %d split pipelined at chunk %u of %lld\n", level, cA, (long long)nchunks);
@@ -970,7 +1102,7 @@ static int covis_reduce(ottohip_ctx* ctx, uint32_t* w0, uint32_t* w1, uint64_t P
       OH_HIP(hipStreamWaitEvent(s2, ctx->ev_half, 0));
       uint32_t* wb0 = w2 ? w2 : w0;  // the next level's buffer of buf-0 tasks
       if (nA[N_SORT]) {
-        launch_hash_range(0, nA[N_SORT], wb0, s2);
+        launch_hash_range(0, nA[N_SORT], wb0, s2, TL.split, lcount + N_SORT + 1, nullptr, 1);
         OH_HIP(hipEventRecord(ctx->ev_hash, s2));
         hash_early = true;
       }
@@ -1054,6 +1186,7 @@ void ottohip_ctx_destroy(ottohip_ctx* ctx) {
   }
   for (auto e : ctx->event_pool) hipEventDestroy(e);
   if (ctx->pinned) hipHostFree(ctx->pinned);
+  if (ctx->level_host) hipHostFree(ctx->level_host);
   delete ctx;
 }
 

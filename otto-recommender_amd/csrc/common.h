@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -102,10 +103,31 @@ struct Ctx {
   // half classified, ev_hash: the next level's first-half hash leaves done
   hipStream_t aux2 = nullptr;
   hipEvent_t ev_half = nullptr, ev_hash = nullptr;
+  // reduce schedule: the hash leaves of a level run on aux2 (ev_hash: done), and the host reads one counter set
+  // per level into level_host (pinned); hash_resident[FOM]: blocks of k_agg_hash<FOM> that fit the device at once
+  // (0: not queried yet)
+  unsigned long long* level_host = nullptr;
+  int hash_resident[4] = {0, 0, 0, 0};
+  int level_buffer() {
+    if (level_host) return 0;
+    if (hipHostMalloc(reinterpret_cast<void**>(&level_host), 32 * sizeof(unsigned long long)) != hipSuccess) {
+      level_host = nullptr;
+      set_error("pinned level buffer allocation failed");
+      return OTTOHIP_ENOMEM;
+    }
+    return 0;
+  }
   int aux_stream() {
     if (aux) return 0;
-    if (hipStreamCreateWithFlags(&aux, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&aux2, hipStreamNonBlocking) != hipSuccess ||
+    // OTTOHIP_AUX_PRIO (read when the streams are created; default 1): the aux stream, whose register sorts have
+    // slack until the next level's classify, gets the device's least stream priority, so the workgroups of the
+    // split on the caller's stream, the critical path, are dispatched ahead of them (step -1.0 ms);
+    // 2 also gives the third stream (hash leaves) the greatest priority; 0: all three at the default priority
+    const int prio = getenv("OTTOHIP_AUX_PRIO") ? atoi(getenv("OTTOHIP_AUX_PRIO")) : 1;
+    int least = 0, greatest = 0;
+    if (prio > 0 && hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = greatest = 0;
+    if (hipStreamCreateWithPriority(&aux, hipStreamNonBlocking, prio > 0 ? least : 0) != hipSuccess ||
+        hipStreamCreateWithPriority(&aux2, hipStreamNonBlocking, prio > 1 ? greatest : 0) != hipSuccess ||
         hipEventCreateWithFlags(&ev_half, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ev_hash, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess ||

@@ -2350,9 +2350,23 @@ struct TaskLists {
   Task* hash;             // workgroup LDS hash (heavy buckets)
   Task* split;            // MSD split
   Task* lds;              // LDS leaf (k_agg_lds)
-  unsigned long long* n;  // [N_SORT + 3]: sort classes..., hash, split, lds
+  unsigned long long* n;  // a counter set: [N_LISTS] sort classes..., hash, split, lds; then LC_CHUNKS.. below
   uint64_t cap;           // capacity of every list
 };
+constexpr int N_LISTS = N_SORT + 3;
+// One counter set of a reduce level (TaskLists::n; two sets, by level parity): the list counts, then what the
+// level's split needs on the host before it can be launched, summed by whoever pushes a split task (the chunks,
+// digits and count-matrix entries of split_work), then the hash leaves' deferred overflow tasks and the error
+// flags of the pushers. The host reads a whole set with one copy.
+constexpr int LC_CHUNKS = N_LISTS, LC_DIGITS = N_LISTS + 1, LC_ENTRIES = N_LISTS + 2, LC_OVERFLOW = N_LISTS + 3,
+              LC_ERR = N_LISTS + 4, LC_WORDS = 16;
+static_assert(LC_ERR < LC_WORDS, "counter set");
+__device__ __forceinline__ uint32_t split_ndig_len(uint64_t len);
+// chunks and digits of the split of a task of len words, as k_split_prepare (entries: their product)
+__device__ __forceinline__ void split_work(uint64_t len, uint32_t& nch, uint32_t& nd) {
+  nch = (uint32_t)((len + 16383ull) / 16384ull);  // SPLIT_CH
+  nd = split_ndig_len(len);
+}
 
 // FOM as k_agg_sort: 0 no FileOpts, 1 cuts / part mode, 3 part mode with the mirror pass, 2 per-file rows only
 template <int FOM = 0>
@@ -2360,8 +2374,14 @@ __global__ __launch_bounds__(AGG_T, 2) void k_agg_hash(const Task* __restrict__ 
                                                     const uint32_t* __restrict__ w0, const uint32_t* __restrict__ w1,
                                                     const uint32_t* __restrict__ row_key, RulesDev R, Layout L,
                                                     int n_rules, OutRows O, Task* __restrict__ overflow,
-                                                    unsigned long long* __restrict__ n_overflow, FileOpts fo) {
+                                                    unsigned long long* __restrict__ n_overflow, FileOpts fo,
+                                                    unsigned int* __restrict__ next_task = nullptr,
+                                                    unsigned long long* __restrict__ ov_work = nullptr) {
+  // next_task: the blocks take their tasks from this counter (zeroed before the launch) in place of the grid
+  // stride, so a grid of only the resident blocks stays balanced over tasks of 1 k to 600 k words.
+  // ov_work: an overflowing task also adds its split's chunks, digits and matrix entries there (LC_CHUNKS..).
   __shared__ unsigned long long lds[2 * HCAP];  // 64 KiB: phase A [0, cap), phase B [0, 2cap)
+  __shared__ unsigned int s_next;
   __shared__ uint32_t wtot[AGG_T / 64];
   __shared__ uint32_t nocc;
   constexpr bool FO = FOM != 0, PM = FOM == 1 || FOM == 3;
@@ -2380,7 +2400,15 @@ __global__ __launch_bounds__(AGG_T, 2) void k_agg_hash(const Task* __restrict__ 
     __syncthreads();
   }
   const bool pmode = PM && fo.parts;
-  for (int64_t ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
+  // (block-uniform; the barriers keep one round's read of s_next apart from the next round's write)
+  auto take_task = [&](int64_t prev) -> int64_t {
+    if (!next_task) return prev < 0 ? (int64_t)blockIdx.x : prev + (int64_t)gridDim.x;
+    __syncthreads();
+    if (tid == 0) s_next = atomicAdd(next_task, 1u);
+    __syncthreads();
+    return (int64_t)s_next;
+  };
+  for (int64_t ti = take_task(-1); ti < n_tasks; ti = take_task(ti)) {
     const Task T = tasks[ti];
     const uint64_t t_start = fo.prof ? wall_clock64() : 0;
     const uint32_t* W = (T.buf ? w1 : w0) + T.begin;
@@ -2462,6 +2490,13 @@ __global__ __launch_bounds__(AGG_T, 2) void k_agg_hash(const Task* __restrict__ 
       if (tid == 0) {
         const unsigned long long k = atomicAdd(n_overflow, 1ull);
         overflow[k] = T;  // capacity = number of hash tasks
+        if (ov_work) {
+          uint32_t nch, nd;
+          split_work(T.len, nch, nd);
+          atomicAdd(ov_work + 0, (unsigned long long)nch);
+          atomicAdd(ov_work + 1, (unsigned long long)nd);
+          atomicAdd(ov_work + 2, (unsigned long long)nch * nd);
+        }
         if (fo.prof) {
           fo.prof[2 * ti] = T.len;
           fo.prof[2 * ti + 1] = (wall_clock64() - t_start) | (1ull << 63);
@@ -2608,14 +2643,15 @@ __device__ __forceinline__ int task_class(uint64_t len, uint32_t level, bool spl
 }
 // Block-aggregated push: every thread of the (256-thread) block must call it once. Per list:
 // LDS counter per block, then one device atomic per list per block.
-constexpr int N_LISTS = N_SORT + 3;
 __device__ __forceinline__ void push_task_block(const TaskLists& TL, bool valid, uint64_t begin, uint64_t len,
                                                 uint32_t row, uint32_t rem, uint32_t buf, bool split, int* err) {
   __shared__ uint32_t bcnt[N_LISTS];
   __shared__ unsigned long long bbase[N_LISTS];
+  __shared__ unsigned long long bwork[3];
   if (valid && len > 0xFFFFFFFFull) { atomicOr(err, 2); valid = false; }
   const int c = valid ? task_class(len, rem, split) : -1;
   if (threadIdx.x < N_LISTS) bcnt[threadIdx.x] = 0;
+  if (threadIdx.x < 3) bwork[threadIdx.x] = 0;
   __syncthreads();
   uint32_t my = 0;
 #pragma unroll
@@ -2626,10 +2662,22 @@ __device__ __forceinline__ void push_task_block(const TaskLists& TL, bool valid,
     if (mbcnt(m) == 0 && c == q) wb = atomicAdd(&bcnt[q], (uint32_t)__popcll(m));
     wb = __shfl(wb, __ffsll((long long)m) - 1);
     if (c == q) my = wb + mbcnt(m);
+    if (q == N_SORT + 1) {  // split tasks: their work totals, per wave, then per block, then one atomic each
+      uint32_t nch = 0, nd = 0;
+      if (c == q) split_work(len, nch, nd);
+      const uint64_t s0 = wave_sum64(nch), s1 = wave_sum64(nd), s2 = wave_sum64((uint64_t)nch * nd);
+      if (lane_id() == 0) {
+        atomicAdd(&bwork[0], (unsigned long long)s0);
+        atomicAdd(&bwork[1], (unsigned long long)s1);
+        atomicAdd(&bwork[2], (unsigned long long)s2);
+      }
+    }
   }
   __syncthreads();
   if (threadIdx.x < N_LISTS && bcnt[threadIdx.x])
     bbase[threadIdx.x] = atomicAdd(&TL.n[threadIdx.x], (unsigned long long)bcnt[threadIdx.x]);
+  if (threadIdx.x >= 64 && threadIdx.x < 67 && bcnt[N_SORT + 1])
+    atomicAdd(&TL.n[LC_CHUNKS + threadIdx.x - 64], bwork[threadIdx.x - 64]);
   __syncthreads();
   if (c >= 0) {
     const unsigned long long k = bbase[c] + my;
@@ -2670,10 +2718,12 @@ constexpr int SPLIT_T = 256;
 // Digits of one split: ceil(len / SPLIT_MEAN), 2..SPLIT_DMAX (any count, not only powers of two), so
 // hashed buckets average <= SPLIT_MEAN words and almost all fit the 512-word register sort.
 constexpr int SPLIT_DMAX = 512;  // digits per split level (512 vs 256: reduce -1 ms same-box; 1024 was slower)
-__device__ __forceinline__ uint32_t split_ndig(const Task& t) {
-  const uint64_t d = ((uint64_t)t.len + c_split_mean - 1) / c_split_mean;
+__device__ __forceinline__ uint32_t split_ndig_len(uint64_t len) {
+  const uint64_t d = (len + c_split_mean - 1) / c_split_mean;
   return d < 2 ? 2u : (d > (uint64_t)SPLIT_DMAX ? (uint32_t)SPLIT_DMAX : (uint32_t)d);
 }
+__device__ __forceinline__ uint32_t split_ndig(const Task& t) { return split_ndig_len(t.len); }
+static_assert(SPLIT_CH == 16384, "split_work");
 // Split digit: a hash of the word's (rule, aid_next) part, seeded by the split level, scaled to
 // nd digits. Every word of one output row (all its files) lands in the same bucket, buckets are
 // balanced whatever the aid_next distribution, and a bucket split again at the next level
