@@ -502,8 +502,10 @@ int ottohip_covis_reduce_received_opts(ottohip_ctx* ctx, const ottohip_rule* rul
                                        const ottohip_file_opts* opts, ottohip_table** out, void* stream);
 
 /* ---- Word2Vec top-K similarity (model/w2vec_aids.py:98-173) ------------------------------
- * Replaces load_index_faiss_ivff (:98-110) + get_top_k_similar_faiss (:125-173): exact L2
- * search (the reference's IVFFlat nlist 100 / nprobe 3 is approximate). The index packs the
+ * Replaces load_index_faiss_ivff (:98-110) + get_top_k_similar_faiss (:125-173): a scan of every
+ * row (the reference's IVFFlat nlist 100 / nprobe 3 probes 3 of 100 lists). ottohip_knn_topk is an
+ * exact L2 search inside the envelope DESIGN.md section 5 states (embeddings centred near the origin, not
+ * tightly clustered); ottohip_knn_topk_exact (below) is exact for every input. The index packs the
  * caller's fp32 embeddings [n_items x dim] (device, kept referenced) into a bf16 MFMA operand;
  * ottohip_knn_topk returns, per query row, the k nearest rows in ascending squared L2
  * distance (ties by row index), distances exact in fp32 (candidates from bf16 MFMA scores,
@@ -515,6 +517,31 @@ int ottohip_knn_index_create(ottohip_ctx* ctx, const float* emb, int64_t n_items
 int ottohip_knn_topk(ottohip_ctx* ctx, const ottohip_knn_index* index, const int32_t* query_rows,
                      int64_t n_q, int k, int32_t* out_idx, float* out_d2, void* stream);
 void ottohip_knn_index_free(ottohip_knn_index* index);
+
+/* Exact mode. ottohip_knn_index_create_ex with OTTOHIP_KNN_CENTER packs the rows as v - mean (the column
+ * mean, summed in double in a fixed order): L2 is translation invariant, and the bf16 scores' error scales
+ * with |q||v|, which a common offset inflates. The index keeps the mean and the largest packed norm; flags 0
+ * packs what ottohip_knn_index_create packs.
+ * ottohip_knn_topk_exact (arguments as ottohip_knn_topk) returns the k rows nearest in fp32 squared L2,
+ * ties by row index among all equal rows, whatever the embeddings look like: the main pass keeps every row
+ * whose bf16 key is within a derived margin of the running 24th best (up to 512 per query), all of them
+ * that can still be among the top k are reranked in fp32, and a query with more than 512 such rows is
+ * answered by an fp32 scan of every row -- correct, and slower where the data is hostile. It accepts an
+ * uncentred index (the margin then comes from the uncentred norms, and the scan keeps the result right).
+ * stats (host, may be NULL): queries answered by the fp32 scan, and the per-query counts of kept rows.
+ * OTTOHIP_KNN_EXACT=1 in the environment (read per call) makes ottohip_knn_index_create behave as
+ * _ex(OTTOHIP_KNN_CENTER) and ottohip_knn_topk as ottohip_knn_topk_exact; unset, nothing changes. */
+#define OTTOHIP_KNN_CENTER 1u
+typedef struct ottohip_knn_exact_stats {
+  int64_t n_overflow;   /* queries redone by the fp32 scan */
+  int64_t max_appends;  /* largest per-query count of rows the main pass kept */
+  int64_t sum_appends;  /* their sum over the queries */
+} ottohip_knn_exact_stats;
+int ottohip_knn_index_create_ex(ottohip_ctx* ctx, const float* emb, int64_t n_items, int dim, unsigned flags,
+                                ottohip_knn_index** out, void* stream);
+int ottohip_knn_topk_exact(ottohip_ctx* ctx, const ottohip_knn_index* index, const int32_t* query_rows,
+                           int64_t n_q, int k, int32_t* out_idx, float* out_d2,
+                           ottohip_knn_exact_stats* stats, void* stream);
 
 /* Test hooks for the device primitives the engine is built from (parity tests only). */
 int ottohip_test_exclusive_scan_u32(ottohip_ctx* ctx, const uint32_t* in, uint64_t* out, int64_t n,

@@ -59,6 +59,13 @@ class MergeParams(ctypes.Structure):
                 ("max_rows", ctypes.c_int64), ("filter_rows", ctypes.c_int64), ("max_rows_groupby", ctypes.c_int64)]
 
 
+class KnnExactStats(ctypes.Structure):
+    _fields_ = [("n_overflow", ctypes.c_int64), ("max_appends", ctypes.c_int64), ("sum_appends", ctypes.c_int64)]
+
+
+KNN_CENTER = 1  # OTTOHIP_KNN_CENTER
+
+
 # name -> (restype, argtypes); the exported symbol set of include/ottohip.h
 _VP, _I32, _I64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
 SIGNATURES = {
@@ -164,6 +171,10 @@ SIGNATURES = {
     "ottohip_knn_index_create": (ctypes.c_int, [_VP, _VP, _I64, ctypes.c_int, ctypes.POINTER(_VP), _VP]),
     "ottohip_knn_topk": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.c_int, _VP, _VP, _VP]),
     "ottohip_knn_index_free": (None, [_VP]),
+    "ottohip_knn_index_create_ex": (ctypes.c_int, [_VP, _VP, _I64, ctypes.c_int, ctypes.c_uint, ctypes.POINTER(_VP),
+                                                   _VP]),
+    "ottohip_knn_topk_exact": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.c_int, _VP, _VP,
+                                              ctypes.POINTER(KnnExactStats), _VP]),
     "ottohip_test_exclusive_scan_u32": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.POINTER(ctypes.c_uint64), _VP]),
     "ottohip_test_radix_sort_pairs": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.c_int, _VP]),
     "ottohip_test_lanes": (ctypes.c_int, [_VP, _VP, _VP]),

@@ -13,6 +13,9 @@
 //      KN_C best (score, item) in a sorted register list, inserting only above the bound.
 //   3. k_knn_rerank: one wave per query recomputes |q - v|^2 exactly in fp32 for the KN_C
 //      candidates and sorts by (d2, index): the top-k rows and their exact squared distances.
+// Exact mode (ottohip_knn_topk_exact, exact for every input): rows packed minus their column mean, k_knn_main<MARGIN>
+// buffering every row within delta(q) of the running KN_C-th best key, k_knn_rerank_buf reranking all of them that
+// can be among the top k, k_knn_scan_f32 scanning every row for a query whose buffer overflowed.
 #include <cmath>
 #include <cstdlib>
 #include "common.h"
@@ -41,9 +44,43 @@ __device__ __forceinline__ uint16_t f2bf(float f) {  // round to nearest even
 }
 __device__ __forceinline__ float bf2f(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
 
-// items (rows of emb) -> packed bf16 with the -|v|^2/2 columns; or queries (rows[q]) with 1, 1
+// Column mean of emb [n x dim] in two deterministic steps (no float atomics): block b sums rows
+// [b * KN_MEAN_ROWS, (b + 1) * KN_MEAN_ROWS) per column in double (row lane rl takes every KN_MEAN_RL-th row, the
+// lanes' sums are added in lane order), then one block adds the partials in block order.
+constexpr int KN_MEAN_ROWS = 1024;
+constexpr int KN_MEAN_RL = 4;
+__global__ __launch_bounds__(KN_KD * KN_MEAN_RL) void k_knn_colsum(const float* __restrict__ emb, int64_t n, int dim,
+                                                                   double* __restrict__ part) {
+  __shared__ double sh[KN_MEAN_RL][KN_KD];
+  const int d = threadIdx.x % KN_KD, rl = threadIdx.x / KN_KD;
+  const int64_t r0 = (int64_t)blockIdx.x * KN_MEAN_ROWS, r1 = r0 + KN_MEAN_ROWS < n ? r0 + KN_MEAN_ROWS : n;
+  double acc = 0.0;
+  if (d < dim)
+    for (int64_t r = r0 + rl; r < r1; r += KN_MEAN_RL) acc += (double)emb[r * dim + d];
+  sh[rl][d] = acc;
+  __syncthreads();
+  if (rl == 0 && d < dim) {
+    for (int j = 1; j < KN_MEAN_RL; ++j) acc += sh[j][d];
+    part[(int64_t)blockIdx.x * dim + d] = acc;
+  }
+}
+__global__ __launch_bounds__(KN_KD) void k_knn_colmean(const double* __restrict__ part, int64_t n_part, int64_t n, int dim,
+                                                       float* __restrict__ mean) {
+  const int d = threadIdx.x;
+  if (d >= dim) return;
+  double acc = 0.0;
+  for (int64_t b = 0; b < n_part; ++b) acc += part[b * dim + d];
+  mean[d] = (float)(acc / (double)n);
+}
+
+// items (rows of emb) -> packed bf16 with the -|v|^2/2 columns; or queries (rows[q]) with 1, 1.
+// mean (optional): the rows are packed centred, x = v[d] - mean[d] in fp32 (L2 distances do not move, the
+// |q||v| that the bf16 error scales with does). norm_out (optional): |x|^2 of the packed row, per query, or
+// for items their maximum (atomicMax on the bits of a non-negative float: independent of the order).
+// With both null the output is what it was without them.
 __global__ void k_knn_pack(const float* __restrict__ emb, int64_t n, int dim, const int32_t* __restrict__ rows,
-                           int64_t n_items, int is_query, uint16_t* __restrict__ out, int* __restrict__ err) {
+                           int64_t n_items, int is_query, uint16_t* __restrict__ out, int* __restrict__ err,
+                           const float* __restrict__ mean = nullptr, float* __restrict__ norm_out = nullptr) {
   const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (i >= n) return;
   const int l = threadIdx.x & 63;
@@ -55,12 +92,16 @@ __global__ void k_knn_pack(const float* __restrict__ emb, int64_t n, int dim, co
   const float* v = emb + src * dim;
   float ss = 0.f;
   for (int d = l; d < KN_KD; d += 64) {
-    float x = d < dim ? v[d] : 0.f;
+    float x = d < dim ? (mean ? v[d] - mean[d] : v[d]) : 0.f;
     ss += x * x;
     out[i * KN_KD + d] = d < dim ? f2bf(x) : 0;
   }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+  if (l == 0 && norm_out) {
+    if (is_query) norm_out[i] = ss;
+    else atomicMax(reinterpret_cast<uint32_t*>(norm_out), __float_as_uint(ss));
+  }
   if (l == 0) {
     if (is_query) {
       out[i * KN_KD + dim] = f2bf(1.f);
@@ -72,6 +113,36 @@ __global__ void k_knn_pack(const float* __restrict__ emb, int64_t n, int dim, co
       out[i * KN_KD + dim + 1] = f2bf(nh - bf2f(hi));
     }
   }
+}
+
+// max |v|^2 over the rows of an index that was packed without it (one wave per row, k_knn_pack's sum)
+__global__ void k_knn_maxnorm(const float* __restrict__ emb, int64_t n, int dim, float* __restrict__ norm_out) {
+  const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (i >= n) return;
+  const int l = threadIdx.x & 63;
+  const float* v = emb + i * dim;
+  float ss = 0.f;
+  for (int d = l; d < KN_KD; d += 64) {
+    const float x = d < dim ? v[d] : 0.f;
+    ss += x * x;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+  if (l == 0) atomicMax(reinterpret_cast<uint32_t*>(norm_out), __float_as_uint(ss));
+}
+
+// The exact search's margin per query: with n = |q'|, N = max |w'| over the packed rows,
+//   Emax = 1.01 * 2^-7 * n N + 2^-15 * (N^2 + n N) + 2^-144  >=  E(q, w) for every row w,
+//   delta = 2 Emax (1 + 2^-20) + 2^-22 (n N + N^2), rounded up to fp32.
+// The last term covers the fp32 rounding of "24th-best key - delta" (half an ulp of a key, |key| <= n N + N^2 / 2
+// + Emax), which the 2^-20 alone does not where the second term of Emax dominates.
+__global__ void k_knn_delta(const float* __restrict__ qn2, const float* __restrict__ maxn2, int64_t nq,
+                            float* __restrict__ delta) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  const double n = sqrt((double)qn2[q]), N = sqrt((double)*maxn2);
+  const double emax = 1.01 * 0x1p-7 * n * N + 0x1p-15 * (N * N + n * N) + 0x1p-144;
+  delta[q] = __double2float_ru(2.0 * emax * (1.0 + 0x1p-20) + 0x1p-22 * (n * N + N * N));
 }
 
 // 64 queries per wave: two 32x32 output blocks (queries qbase + [0, 32) and qbase + [32, 64))
@@ -105,12 +176,18 @@ __device__ __forceinline__ s16x4 lo4(const bf16x8& v) {  // the low 4 bf16 of a 
 // HALF: the last k-step covers 8 columns with v_mfma_f32_32x32x8_bf16 (dim + 2 <= 16 (KS - 1) + 8: dim 100 -> 104
 //   columns instead of 112; the 14th chunk of a row is neither streamed nor multiplied).
 constexpr int KN_BCAP = 512;  // inserted candidates kept per query (overflow: the search reruns with index lists)
-template <int ABL, int KS, bool BUF = false, bool HALF = false>
+// MARGIN (BUF, MODE 0; the exact search): a row is appended when its key beats the running KN_C-th best key minus
+//   the query's delta[q] (k_knn_delta), so the threshold of the block gate and of the append loop is
+//   sc[KN_C - 1] - delta (with a pre-pass the list starts at its bound b: b - delta until KN_C keys above b are in).
+//   The score list is untouched by the rows inside the margin: med3(sc[j-1], s, sc[j]) with s < sc[KN_C-1] keeps sc[j].
+template <int ABL, int KS, bool BUF = false, bool HALF = false, bool MARGIN = false>
 __global__ __launch_bounds__(KN_T) void k_knn_main(const uint4* __restrict__ items, int64_t V,
                                                   const uint4* __restrict__ queries, int64_t nq,
                                                   uint32_t* __restrict__ cand, float* __restrict__ thr_io,
                                                   int pre_stride, uint2* __restrict__ cbuf = nullptr,
-                                                  uint32_t* __restrict__ ncand = nullptr) {
+                                                  uint32_t* __restrict__ ncand = nullptr,
+                                                  const float* __restrict__ delta = nullptr) {
+  static_assert(!MARGIN || (BUF && ABL == 0), "the margin is a mode of the buffered full scan");
   __shared__ uint4 ring[KN_RING * KN_IT * KN_CH];  // 2 x 64 KiB, the only LDS object
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, r = l & 31, h = l >> 5;
   const int64_t qbase = (int64_t)blockIdx.x * KN_QB + w * 64;
@@ -139,6 +216,8 @@ __global__ __launch_bounds__(KN_T) void k_knn_main(const uint4* __restrict__ ite
 #pragma unroll
   for (int j = 0; j < KN_C; ++j) { sc[j] = -INFINITY; ix[j] = 0xFFFFFFFFu; }
   float thr = -INFINITY;
+  float dlt = 0.f;
+  if constexpr (MARGIN) dlt = q < nq ? delta[q] : 0.f;
   constexpr bool PRE = ABL == 2;
   const int64_t nTall = ceil_div(V, KN_IT);
   const int64_t nT = PRE ? (nTall - 1 + pre_stride - 1) / pre_stride : nTall;  // tiles scanned
@@ -146,7 +225,7 @@ __global__ __launch_bounds__(KN_T) void k_knn_main(const uint4* __restrict__ ite
     const float b = q < nq ? thr_io[q] : -INFINITY;
 #pragma unroll
     for (int j = 0; j < KN_C; ++j) sc[j] = b;
-    thr = b;
+    thr = MARGIN ? b - dlt : b;
   }
   // LDS chunk p = u*512 + tid holds item row p>>4, source chunk (p & 15) ^ (row & 15);
   // rows past V read row V-1 (valid memory; their scores are masked below); source chunks past
@@ -181,7 +260,7 @@ __global__ __launch_bounds__(KN_T) void k_knn_main(const uint4* __restrict__ ite
           sc[j] = __builtin_amdgcn_fmed3f(sc[j - 1], s_, sc[j]);
         }
         sc[0] = fmaxf(sc[0], s_);
-        thr = sc[KN_C - 1];
+        thr = MARGIN ? sc[KN_C - 1] - dlt : sc[KN_C - 1];
         return;
       }
     }
@@ -371,6 +450,173 @@ __global__ __launch_bounds__(256) void k_knn_select_buf(const uint2* __restrict_
   }
 }
 
+// exact fp32 |q - v|^2: one operation order for every rerank, so their distances are bit-equal
+__device__ __forceinline__ float knn_d2(const float* __restrict__ qv, const float* __restrict__ v, int dim) {
+  float acc = 0.f;
+  if ((dim & 3) == 0) {  // rows are 16-B aligned: vector loads
+    const float4* q4 = reinterpret_cast<const float4*>(qv);
+    const float4* v4 = reinterpret_cast<const float4*>(v);
+    for (int d = 0; d < dim / 4; ++d) {
+      const float4 a = q4[d], b = v4[d];
+      float t = a.x - b.x; acc = fmaf(t, t, acc);
+      t = a.y - b.y; acc = fmaf(t, t, acc);
+      t = a.z - b.z; acc = fmaf(t, t, acc);
+      t = a.w - b.w; acc = fmaf(t, t, acc);
+    }
+  } else {
+    for (int d = 0; d < dim; ++d) {
+      const float t = qv[d] - v[d];
+      acc = fmaf(t, t, acc);
+    }
+  }
+  return acc;
+}
+// (d2 bits, index) keys: d2 >= 0, so its bits order like the float; KN_NOKEY (inf, no index) sorts last
+constexpr uint64_t KN_NOKEY = ((uint64_t)0x7F800000u << 32) | 0xFFFFFFFFu;
+__device__ __forceinline__ uint64_t knn_sort64(uint64_t key, uint32_t l) {  // bitonic sort, ascending over the wave
+#pragma unroll
+  for (int kk = 2; kk <= 64; kk <<= 1) {
+#pragma unroll
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      const uint64_t o = shfl64(key, (int)(l ^ (uint32_t)j));
+      const bool up = (l & kk) == 0, lower = (l & j) == 0;
+      key = (lower == up) ? (key < o ? key : o) : (key > o ? key : o);
+    }
+  }
+  return key;
+}
+// the 64 smallest of two ascending runs of 64: min(best[l], run[63 - l]) holds them as a bitonic sequence,
+// which one bitonic merge sorts
+__device__ __forceinline__ uint64_t knn_merge64(uint64_t best, uint64_t run, uint32_t l) {
+  const uint64_t rv = shfl64(run, (int)(63u - l));
+  uint64_t key = best < rv ? best : rv;
+#pragma unroll
+  for (int j = 32; j > 0; j >>= 1) {
+    const uint64_t o = shfl64(key, (int)(l ^ (uint32_t)j));
+    key = ((l & j) == 0) ? (key < o ? key : o) : (key > o ? key : o);
+  }
+  return key;
+}
+__device__ __forceinline__ void knn_write_topk(uint64_t key, uint32_t l, int64_t q, int k, int64_t V,
+                                               int32_t* __restrict__ out_idx, float* __restrict__ out_d2) {
+  if ((int)l < k) {
+    const uint32_t idx = (uint32_t)key;
+    out_idx[q * k + l] = idx < (uint32_t)V ? (int32_t)idx : -1;
+    out_d2[q * k + l] = __uint_as_float((uint32_t)(key >> 32));
+  }
+}
+
+// Exact search, one wave per query: the buffer entries whose key is above (KN_C-th largest buffered key - delta)
+// -- the others cannot be among the top k -- are reranked by exact fp32 distance, 64 at a
+// time: sort the 64 (d2, index) keys, merge with the running best 64. A query with more than KN_BCAP appends goes
+// to the overflow list instead (k_knn_scan_f32 answers it).
+__global__ __launch_bounds__(256) void k_knn_rerank_buf(const float* __restrict__ emb, int64_t V, int dim,
+                                                        const int32_t* __restrict__ qrows, int64_t nq,
+                                                        const uint2* __restrict__ cbuf, const uint32_t* __restrict__ ncand,
+                                                        const float* __restrict__ delta, int k,
+                                                        int32_t* __restrict__ out_idx, float* __restrict__ out_d2,
+                                                        uint32_t* __restrict__ n_ovf, uint32_t* __restrict__ ovf_list) {
+  __shared__ uint32_t keep[4][KN_BCAP];
+  const int64_t q = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int w = threadIdx.x >> 6;
+  const uint32_t l = lane_id();
+  if (q >= nq) return;
+  const uint32_t nc = ncand[q];
+  if (nc > (uint32_t)KN_BCAP) {
+    if (l == 0) ovf_list[atomicAdd(n_ovf, 1u)] = (uint32_t)q;
+    return;
+  }
+  constexpr int NE = KN_BCAP / 64;  // entries per lane
+  const uint2* b = cbuf + (size_t)q * KN_BCAP;
+  uint32_t ord[NE], item[NE];  // ord ascends with the key; 0 (below every key) past the entries
+#pragma unroll
+  for (int j = 0; j < NE; ++j) {
+    const uint32_t i = l + 64u * j;
+    ord[j] = 0u; item[j] = 0xFFFFFFFFu;
+    if (i < nc) {
+      const uint2 e = b[i];
+      ord[j] = (e.x & 0x80000000u) ? ~e.x : (e.x | 0x80000000u);
+      item[j] = e.y;
+    }
+  }
+  // the KN_C-th largest ord, bit by bit: the largest t with at least KN_C entries >= t
+  uint32_t t = 0u;
+  if (nc >= (uint32_t)KN_C) {
+    for (int bit = 31; bit >= 0; --bit) {
+      const uint32_t c = t | (1u << bit);
+      uint32_t cnt = 0;
+#pragma unroll
+      for (int j = 0; j < NE; ++j) cnt += (uint32_t)__popcll(__ballot(ord[j] >= c));
+      if (cnt >= (uint32_t)KN_C) t = c;
+    }
+  }
+  const float k24 = __uint_as_float((t & 0x80000000u) ? (t & 0x7FFFFFFFu) : ~t);
+  const float cut = nc >= (uint32_t)KN_C ? k24 - delta[q] : -INFINITY;
+  uint32_t nk = 0;
+#pragma unroll
+  for (int j = 0; j < NE; ++j) {
+    const float key = __uint_as_float((ord[j] & 0x80000000u) ? (ord[j] & 0x7FFFFFFFu) : ~ord[j]);
+    const bool kp = l + 64u * j < nc && key > cut;
+    const uint64_t m = __ballot(kp);
+    if (kp) keep[w][nk + mbcnt(m)] = item[j];
+    nk += (uint32_t)__popcll(m);
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  int64_t qr = qrows ? qrows[q] : q;
+  if (qr < 0 || qr >= V) qr = 0;  // flagged by k_knn_pack; the call returns an error
+  const float* qv = emb + qr * dim;
+  uint64_t best = KN_NOKEY;
+  for (uint32_t base = 0; base < nk; base += 64) {
+    const uint32_t c = base + l < nk ? keep[w][base + l] : 0xFFFFFFFFu;
+    uint64_t key = KN_NOKEY;
+    if (c < (uint32_t)V) key = ((uint64_t)__float_as_uint(knn_d2(qv, emb + (int64_t)c * dim, dim)) << 32) | c;
+    best = knn_merge64(best, knn_sort64(key, l), l);
+  }
+  knn_write_topk(best, l, q, k, V, out_idx, out_d2);
+}
+
+// Exact search, one workgroup per overflowed query: every row's exact fp32 distance. Wave w takes the 64-row
+// groups w, w + KN_SCAN_W, ...; a group is sorted and merged into the wave's best 64 only when one of its keys is
+// below the 64th of them; the waves' lists are merged through LDS.
+constexpr int KN_SCAN_W = 16;
+__global__ __launch_bounds__(64 * KN_SCAN_W) void k_knn_scan_f32(const float* __restrict__ emb, int64_t V, int dim,
+                                                                const int32_t* __restrict__ qrows,
+                                                                const uint32_t* __restrict__ ovf_list, int k,
+                                                                int32_t* __restrict__ out_idx, float* __restrict__ out_d2) {
+  __shared__ uint64_t part[KN_SCAN_W][64];
+  const int w = threadIdx.x >> 6;
+  const uint32_t l = lane_id();
+  const int64_t q = ovf_list[blockIdx.x];
+  int64_t qr = qrows ? qrows[q] : q;
+  if (qr < 0 || qr >= V) qr = 0;
+  const float* qv = emb + qr * dim;
+  uint64_t best = KN_NOKEY;
+  for (int64_t base = (int64_t)w * 64; base < V; base += 64 * KN_SCAN_W) {
+    const int64_t row = base + l;
+    uint64_t key = KN_NOKEY;
+    if (row < V) key = ((uint64_t)__float_as_uint(knn_d2(qv, emb + row * dim, dim)) << 32) | (uint32_t)row;
+    if (__ballot(key < shfl64(best, 63))) best = knn_merge64(best, knn_sort64(key, l), l);
+  }
+  part[w][l] = best;
+  __syncthreads();
+  if (w != 0) return;
+  for (int o = 1; o < KN_SCAN_W; ++o) best = knn_merge64(best, part[o][l], l);
+  knn_write_topk(best, l, q, k, V, out_idx, out_d2);
+}
+
+// appends per query of an exact search: st[1] = max, st[2..3] = sum (uint64), one atomic pair per wave
+__global__ void k_knn_append_stats(const uint32_t* __restrict__ ncand, int64_t nq, uint32_t* __restrict__ st) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t n = q < nq ? ncand[q] : 0u;
+  const uint32_t mx = (uint32_t)__builtin_amdgcn_readlane((int)dpp_incl_scan<true>(n), 63);
+  const uint64_t sum = wave_sum64(n);
+  if (lane_id() == 0) {
+    atomicMax(st + 1, mx);
+    atomicAdd(reinterpret_cast<unsigned long long*>(st + 2), (unsigned long long)sum);
+  }
+}
+
 // one wave per query: exact fp32 |q - v|^2 of the 64 candidates, sorted by (d2, index)
 __global__ __launch_bounds__(256) void k_knn_rerank(const float* __restrict__ emb, int64_t V, int dim,
                                                     const int32_t* __restrict__ qrows, int64_t nq,
@@ -384,43 +630,9 @@ __global__ __launch_bounds__(256) void k_knn_rerank(const float* __restrict__ em
   if (qr < 0 || qr >= V) qr = 0;  // flagged by k_knn_pack; the call returns an error
   const float* qv = emb + qr * dim;
   float d2 = INFINITY;
-  if (c < (uint32_t)V) {
-    const float* v = emb + (int64_t)c * dim;
-    float acc = 0.f;
-    if ((dim & 3) == 0) {  // rows are 16-B aligned: vector loads
-      const float4* q4 = reinterpret_cast<const float4*>(qv);
-      const float4* v4 = reinterpret_cast<const float4*>(v);
-      for (int d = 0; d < dim / 4; ++d) {
-        const float4 a = q4[d], b = v4[d];
-        float t = a.x - b.x; acc = fmaf(t, t, acc);
-        t = a.y - b.y; acc = fmaf(t, t, acc);
-        t = a.z - b.z; acc = fmaf(t, t, acc);
-        t = a.w - b.w; acc = fmaf(t, t, acc);
-      }
-    } else {
-      for (int d = 0; d < dim; ++d) {
-        const float t = qv[d] - v[d];
-        acc = fmaf(t, t, acc);
-      }
-    }
-    d2 = acc;
-  }
-  // bitonic sort of 64 (d2 bits, index) keys; d2 >= 0 so its bits order like the float
-  uint64_t key = ((uint64_t)__float_as_uint(d2) << 32) | c;
-#pragma unroll
-  for (int kk = 2; kk <= 64; kk <<= 1) {
-#pragma unroll
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      const uint64_t o = shfl64(key, (int)(l ^ (uint32_t)j));
-      const bool up = (l & kk) == 0, lower = (l & j) == 0;
-      key = (lower == up) ? (key < o ? key : o) : (key > o ? key : o);
-    }
-  }
-  if ((int)l < k) {
-    const uint32_t idx = (uint32_t)key;
-    out_idx[q * k + l] = idx < (uint32_t)V ? (int32_t)idx : -1;
-    out_d2[q * k + l] = __uint_as_float((uint32_t)(key >> 32));
-  }
+  if (c < (uint32_t)V) d2 = knn_d2(qv, emb + (int64_t)c * dim, dim);
+  const uint64_t key = knn_sort64(((uint64_t)__float_as_uint(d2) << 32) | c, l);
+  knn_write_topk(key, l, q, k, V, out_idx, out_d2);
 }
 
 }  // namespace ottohip
@@ -435,26 +647,78 @@ struct ottohip_knn_index {
   int dim;
   const float* emb;      // caller-owned fp32 [n_items x dim]
   uint16_t* packed;      // bf16 [n_items x 128]
+  unsigned flags;        // OTTOHIP_KNN_CENTER: the packed rows are v - mean
+  float* mean;           // fp32 [dim] column mean (device; null: not centred)
+  float* max_norm;       // max |packed row|^2 before the bf16 rounding (device; null: not computed)
+  float* stat;           // the allocation behind mean and max_norm (fp32 [KN_KD + 1]; null: neither)
 };
+}  // extern "C"
 
-int ottohip_knn_index_create(ottohip_ctx* c, const float* emb, int64_t n_items, int dim,
-                             ottohip_knn_index** out, void* stream) {
-  if (!c || !emb || !out || n_items < 1 || dim < 1 || dim > KN_KD - 2 || n_items >= (int64_t)0xFFFFFFFFu) {
+static bool env_is(const char* name, const char* value) {  // read per call
+  const char* v = getenv(name);
+  return v && !strcmp(v, value);
+}
+
+// with_norm: also keep max_norm (the exact search's margin needs it); flags 0 without it packs and launches what
+// the index always did
+static int knn_index_build(ottohip_ctx* c, const float* emb, int64_t n_items, int dim, unsigned flags, bool with_norm,
+                           ottohip_knn_index** out, void* stream) {
+  if (!c || !emb || !out || n_items < 1 || dim < 1 || dim > KN_KD - 2 || n_items >= (int64_t)0xFFFFFFFFu ||
+      (flags & ~(unsigned)OTTOHIP_KNN_CENTER)) {
     set_error("knn_index_create: bad arguments (dim must be <= %d)", KN_KD - 2);
     return OTTOHIP_EINVAL;
   }
   Ctx* ctx = ctx_base(c);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   ottohip_knn_index* ix = new ottohip_knn_index();
-  ix->device = ctx->device; ix->n_items = n_items; ix->dim = dim; ix->emb = emb;
-  if (dev_alloc(reinterpret_cast<void**>(&ix->packed), (size_t)n_items * KN_KD * 2, "knn_packed") != hipSuccess) {
+  ix->device = ctx->device; ix->n_items = n_items; ix->dim = dim; ix->emb = emb; ix->flags = flags;
+  float*& stat = ix->stat;
+  if (dev_alloc(reinterpret_cast<void**>(&ix->packed), (size_t)n_items * KN_KD * 2, "knn_packed") != hipSuccess ||
+      ((flags || with_norm) && dev_alloc(reinterpret_cast<void**>(&stat), (KN_KD + 1) * sizeof(float), "knn_stat") != hipSuccess)) {
+    if (ix->packed) dev_free(ix->packed);
     delete ix; set_error("knn_index_create: allocation failed"); return OTTOHIP_ENOMEM;
   }
-  k_knn_pack<<<(unsigned)ceil_div(n_items * 64, 256), 256, 0, s>>>(emb, n_items, dim, nullptr, n_items, 0, ix->packed,
-                                                                   nullptr);
-  OH_HIP(hipGetLastError());
+  if (stat) {
+    if (hipMemsetAsync(stat, 0, (KN_KD + 1) * sizeof(float), s) != hipSuccess) {
+      dev_free(stat); dev_free(ix->packed); delete ix; set_error("knn_index_create: memset failed"); return OTTOHIP_EHIP;
+    }
+    ix->mean = (flags & OTTOHIP_KNN_CENTER) ? stat : nullptr;
+    ix->max_norm = with_norm ? stat + KN_KD : nullptr;
+  }
+  int rc = 0;
+  if (ix->mean) {
+    const int64_t nb = ceil_div(n_items, KN_MEAN_ROWS);
+    double* part;
+    rc = ctx->ws.get("knn_colsum", (size_t)nb * dim, &part);
+    if (rc == 0) {
+      k_knn_colsum<<<(unsigned)nb, KN_KD * KN_MEAN_RL, 0, s>>>(emb, n_items, dim, part);
+      k_knn_colmean<<<1, KN_KD, 0, s>>>(part, nb, n_items, dim, ix->mean);
+    }
+  }
+  if (rc == 0) {
+    k_knn_pack<<<(unsigned)ceil_div(n_items * 64, 256), 256, 0, s>>>(emb, n_items, dim, nullptr, n_items, 0, ix->packed,
+                                                                     nullptr, ix->mean, ix->max_norm);
+    if (hipGetLastError() != hipSuccess) { set_error("knn_index_create: launch failed"); rc = OTTOHIP_EHIP; }
+  }
+  if (rc != 0) {
+    if (stat) dev_free(stat);
+    dev_free(ix->packed); delete ix; return rc;
+  }
   *out = ix;
   return 0;
+}
+
+extern "C" {
+
+int ottohip_knn_index_create(ottohip_ctx* c, const float* emb, int64_t n_items, int dim,
+                             ottohip_knn_index** out, void* stream) {
+  const bool exact = env_is("OTTOHIP_KNN_EXACT", "1");  // then as _ex(OTTOHIP_KNN_CENTER)
+  return knn_index_build(c, emb, n_items, dim, exact ? OTTOHIP_KNN_CENTER : 0u, exact, out, stream);
+}
+
+int ottohip_knn_index_create_ex(ottohip_ctx* c, const float* emb, int64_t n_items, int dim, unsigned flags,
+                                ottohip_knn_index** out, void* stream) {
+  return knn_index_build(c, emb, n_items, dim, flags, true, out, stream);
 }
 
 void ottohip_knn_index_free(ottohip_knn_index* ix) {
@@ -462,11 +726,13 @@ void ottohip_knn_index_free(ottohip_knn_index* ix) {
   (void)hipSetDevice(ix->device);
   (void)hipDeviceSynchronize();
   dev_free(ix->packed);
+  if (ix->stat) dev_free(ix->stat);
   delete ix;
 }
 
 int ottohip_knn_topk(ottohip_ctx* c, const ottohip_knn_index* ix, const int32_t* query_rows, int64_t n_q, int k,
                      int32_t* out_idx, float* out_d2, void* stream) {
+  if (env_is("OTTOHIP_KNN_EXACT", "1")) return ottohip_knn_topk_exact(c, ix, query_rows, n_q, k, out_idx, out_d2, nullptr, stream);
   // an empty query set has empty outputs, whose device pointers may be null
   if (!c || !ix || n_q < 0 || k < 1 || k > KN_KMAX || (n_q > 0 && (!out_idx || !out_d2))) {
     set_error("knn_topk: bad arguments (1 <= k <= %d)", KN_KMAX);
@@ -489,7 +755,8 @@ int ottohip_knn_topk(ottohip_ctx* c, const ottohip_knn_index* ix, const int32_t*
   OH_TRY(ctx->ws.get("knn_err", 1, &err));
   OH_HIP(hipMemsetAsync(err, 0, sizeof(int), s));
   int ph = ctx->begin("knn_pack", s, 0);
-  k_knn_pack<<<(unsigned)ceil_div(n_q * 64, 256), 256, 0, s>>>(ix->emb, n_q, ix->dim, query_rows, ix->n_items, 1, qp, err);
+  k_knn_pack<<<(unsigned)ceil_div(n_q * 64, 256), 256, 0, s>>>(ix->emb, n_q, ix->dim, query_rows, ix->n_items, 1, qp, err,
+                                                               ix->mean, nullptr);  // a centred index takes centred queries
   ctx->end(ph, s);
   static const int abl = getenv("OTTOHIP_KNN_ABLATE") ? atoi(getenv("OTTOHIP_KNN_ABLATE")) : 0;
   static const int nopre = getenv("OTTOHIP_KNN_NOPRE") ? atoi(getenv("OTTOHIP_KNN_NOPRE")) : 0;
@@ -506,7 +773,7 @@ int ottohip_knn_topk(ottohip_ctx* c, const ottohip_knn_index* ix, const int32_t*
     const int64_t nS = (nT - 1 + pst - 1) / pst;
     ph = ctx->begin("knn_pre", s, 2.0 * (double)n_q * (double)(nS * KN_IT) * ix->dim);
     (k8 ? k_knn_main<2, 8> : (half ? k_knn_main<2, 7, false, true> : k_knn_main<2, 7>))<<<grid, KN_T, 0, s>>>(reinterpret_cast<const uint4*>(ix->packed), ix->n_items,
-                                          reinterpret_cast<const uint4*>(qp), n_q, cand, thr, pst, nullptr, nullptr);
+                                          reinterpret_cast<const uint4*>(qp), n_q, cand, thr, pst, nullptr, nullptr, nullptr);
     ctx->end(ph, s);
   }
   ph = ctx->begin("knn_main", s, 2.0 * (double)n_q * (double)ix->n_items * ix->dim);
@@ -523,7 +790,7 @@ int ottohip_knn_topk(ottohip_ctx* c, const ottohip_knn_index* ix, const int32_t*
     OH_HIP(hipMemsetAsync(ovf, 0, sizeof(int), s));
     (k8 ? k_knn_main<0, 8, true> : (half ? k_knn_main<0, 7, true, true> : k_knn_main<0, 7, true>))<<<grid, KN_T, 0, s>>>(
         reinterpret_cast<const uint4*>(ix->packed), ix->n_items, reinterpret_cast<const uint4*>(qp), n_q, cand, thr, pst,
-        cbuf, ncand);
+        cbuf, ncand, nullptr);
     ctx->end(ph, s);
     ph = ctx->begin("knn_select", s, 0);
     k_knn_select_buf<<<(unsigned)ceil_div(n_q * 64, 256), 256, 0, s>>>(cbuf, ncand, n_q, cand, ovf);
@@ -538,7 +805,7 @@ int ottohip_knn_topk(ottohip_ctx* c, const ottohip_knn_index* ix, const int32_t*
     auto kmain = k8 ? (abl == 3 ? k_knn_main<3, 8> : (abl ? k_knn_main<1, 8> : k_knn_main<0, 8>))
                     : (abl == 3 ? k_knn_main<3, 7> : (abl ? k_knn_main<1, 7> : (half ? k_knn_main<0, 7, false, true> : k_knn_main<0, 7>)));
     kmain<<<grid, KN_T, 0, s>>>(reinterpret_cast<const uint4*>(ix->packed), ix->n_items,
-                                reinterpret_cast<const uint4*>(qp), n_q, cand, thr, pst, nullptr, nullptr);
+                                reinterpret_cast<const uint4*>(qp), n_q, cand, thr, pst, nullptr, nullptr, nullptr);
     ctx->end(ph, s);
   }
   ph = ctx->begin("knn_rerank", s, 0);
@@ -552,6 +819,93 @@ int ottohip_knn_topk(ottohip_ctx* c, const ottohip_knn_index* ix, const int32_t*
     OH_HIP(hipStreamSynchronize(s));
     if (herr) { set_error("knn_topk: a query row is outside [0, n_items)"); return OTTOHIP_ERANGE; }
   }
+  return 0;
+}
+
+// The exact search: the main pass appends every row whose key is within delta(q) of the
+// running KN_C-th best, k_knn_rerank_buf reranks what can still be among the top k in fp32, and a query whose buffer
+// overflowed is answered by k_knn_scan_f32 over all rows. One pass over the items, whatever they look like.
+int ottohip_knn_topk_exact(ottohip_ctx* c, const ottohip_knn_index* ix, const int32_t* query_rows, int64_t n_q, int k,
+                           int32_t* out_idx, float* out_d2, ottohip_knn_exact_stats* stats, void* stream) {
+  if (!c || !ix || n_q < 0 || k < 1 || k > KN_KMAX || (n_q > 0 && (!out_idx || !out_d2))) {
+    set_error("knn_topk_exact: bad arguments (1 <= k <= %d)", KN_KMAX);
+    return OTTOHIP_EINVAL;
+  }
+  if (stats) *stats = ottohip_knn_exact_stats{0, 0, 0};
+  if (n_q == 0) return 0;
+  if (!query_rows && n_q > ix->n_items) {
+    set_error("knn_topk_exact: n_q=%lld query rows 0..n_q-1 exceed the index (%lld rows)", (long long)n_q,
+              (long long)ix->n_items);
+    return OTTOHIP_EINVAL;
+  }
+  Ctx* ctx = ctx_base(c);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  ctx->reset_timing();
+  uint16_t* qp;
+  float *qn2, *delta, *thr = nullptr;
+  uint2* cbuf;
+  uint32_t *ncand, *ovf_list;
+  uint32_t* st;  // [0] overflowed queries, [1] max appends, [2..3] sum of appends (uint64), [4] bad query row, [5] max norm
+  OH_TRY(ctx->ws.get("knn_q", (size_t)n_q * KN_KD * 2, reinterpret_cast<void**>(&qp)));
+  OH_TRY(ctx->ws.get("knn_qn2", (size_t)n_q, &qn2));
+  OH_TRY(ctx->ws.get("knn_delta", (size_t)n_q, &delta));
+  OH_TRY(ctx->ws.get("knn_cbuf", (size_t)n_q * KN_BCAP, &cbuf));
+  OH_TRY(ctx->ws.get("knn_ncand", (size_t)n_q, &ncand));
+  OH_TRY(ctx->ws.get("knn_ovf_list", (size_t)n_q, &ovf_list));
+  OH_TRY(ctx->ws.get("knn_xstat", 8, &st));
+  OH_HIP(hipMemsetAsync(st, 0, 8 * sizeof(uint32_t), s));
+  int ph = ctx->begin("knn_pack", s, 0);
+  const float* maxn2 = ix->max_norm;
+  if (!maxn2) {  // an index made without it: the margin comes from the uncentred rows' norms
+    float* m = reinterpret_cast<float*>(st + 5);
+    k_knn_maxnorm<<<(unsigned)ceil_div(ix->n_items * 64, 256), 256, 0, s>>>(ix->emb, ix->n_items, ix->dim, m);
+    maxn2 = m;
+  }
+  k_knn_pack<<<(unsigned)ceil_div(n_q * 64, 256), 256, 0, s>>>(ix->emb, n_q, ix->dim, query_rows, ix->n_items, 1, qp,
+                                                               reinterpret_cast<int*>(st + 4), ix->mean, qn2);
+  k_knn_delta<<<(unsigned)ceil_div(n_q, 256), 256, 0, s>>>(qn2, maxn2, n_q, delta);
+  ctx->end(ph, s);
+  static const int nopre = getenv("OTTOHIP_KNN_NOPRE") ? atoi(getenv("OTTOHIP_KNN_NOPRE")) : 0;
+  static const int pst = getenv("OTTOHIP_KNN_PRE_STRIDE") ? std::max(2, atoi(getenv("OTTOHIP_KNN_PRE_STRIDE"))) : PRE_STRIDE;
+  const unsigned grid = (unsigned)ceil_div(n_q, KN_QB);
+  const int64_t nT = ceil_div(ix->n_items, KN_IT);
+  const bool k8 = ix->dim + 2 > 7 * 16;
+  const bool half = !k8 && ix->dim + 2 <= 6 * 16 + 8 && !env_is("OTTOHIP_KNN_HALF", "0");
+  const uint4* items = reinterpret_cast<const uint4*>(ix->packed);
+  const uint4* queries = reinterpret_cast<const uint4*>(qp);
+  if (!nopre && (nT - 1) / pst >= KN_C) {  // the default search's pre-pass: a lower bound of the KN_C-th best key
+    OH_TRY(ctx->ws.get("knn_thr", (size_t)n_q, &thr));
+    const int64_t nS = (nT - 1 + pst - 1) / pst;
+    ph = ctx->begin("knn_pre", s, 2.0 * (double)n_q * (double)(nS * KN_IT) * ix->dim);
+    (k8 ? k_knn_main<2, 8> : (half ? k_knn_main<2, 7, false, true> : k_knn_main<2, 7>))<<<grid, KN_T, 0, s>>>(
+        items, ix->n_items, queries, n_q, nullptr, thr, pst, nullptr, nullptr, nullptr);
+    ctx->end(ph, s);
+  }
+  ph = ctx->begin("knn_main", s, 2.0 * (double)n_q * (double)ix->n_items * ix->dim);
+  (k8 ? k_knn_main<0, 8, true, false, true> : (half ? k_knn_main<0, 7, true, true, true> : k_knn_main<0, 7, true, false, true>))
+      <<<grid, KN_T, 0, s>>>(items, ix->n_items, queries, n_q, nullptr, thr, pst, cbuf, ncand, delta);
+  ctx->end(ph, s);
+  ph = ctx->begin("knn_rerank_buf", s, 0);
+  k_knn_rerank_buf<<<(unsigned)ceil_div(n_q * 64, 256), 256, 0, s>>>(ix->emb, ix->n_items, ix->dim, query_rows, n_q, cbuf,
+                                                                     ncand, delta, k, out_idx, out_d2, st, ovf_list);
+  if (stats) k_knn_append_stats<<<(unsigned)ceil_div(n_q, 256), 256, 0, s>>>(ncand, n_q, st);
+  ctx->end(ph, s);
+  OH_HIP(hipGetLastError());
+  uint32_t hst[8];
+  OH_HIP(hipMemcpyAsync(hst, st, sizeof(hst), hipMemcpyDeviceToHost, s));
+  OH_HIP(hipStreamSynchronize(s));
+  if (hst[0]) {  // queries with more than KN_BCAP appends: every row in fp32
+    ph = ctx->begin("knn_scan_f32", s, (double)hst[0] * (double)ix->n_items * ix->dim * 4.0);
+    k_knn_scan_f32<<<hst[0], 64 * KN_SCAN_W, 0, s>>>(ix->emb, ix->n_items, ix->dim, query_rows, ovf_list, k, out_idx, out_d2);
+    ctx->end(ph, s);
+    OH_HIP(hipGetLastError());
+  }
+  if (stats) {
+    stats->n_overflow = hst[0];
+    stats->max_appends = hst[1];
+    stats->sum_appends = (int64_t)(((uint64_t)hst[3] << 32) | hst[2]);
+  }
+  if (hst[4]) { set_error("knn_topk_exact: a query row is outside [0, n_items)"); return OTTOHIP_ERANGE; }
   return 0;
 }
 }  // extern "C"

@@ -51,11 +51,11 @@ def _deal(fb, rank, world):
     return deal_files(n_files, rank, world, [float(fb[f + 1] - fb[f]) for f in range(n_files)])
 
 
-def _knn_lists(words, emb, knn_queries, ctx, dev, group):
+def _knn_lists(words, emb, knn_queries, ctx, dev, group, exact=False):
     """B3 for the first knn_queries vocabulary rows; with a group the queries are split in equal
     ranges over ranks (the item matrix is replicated) and the lists all-gathered."""
     import torch
-    idx = KnnIndex(emb, ctx)
+    idx = KnnIndex(emb, ctx, center=exact)
     nq = min(knn_queries, idx.n_items)
     q0, q1 = 0, nq
     if group is not None:
@@ -63,7 +63,7 @@ def _knn_lists(words, emb, knn_queries, ctx, dev, group):
         r, g = dist.get_rank(group), dist.get_world_size(group)
         q0, q1 = (nq * r) // g, (nq * (r + 1)) // g
     rows = torch.arange(q0, q1, dtype=torch.int32, device=dev)
-    i, _ = idx.search(rows, k=config.W2VEC_K) if q1 > q0 else (torch.empty((0, config.W2VEC_K), dtype=torch.int32,
+    i, _ = idx.search(rows, k=config.W2VEC_K, exact=exact) if q1 > q0 else (torch.empty((0, config.W2VEC_K), dtype=torch.int32,
                                                                             device=dev), None)
     idx.free()
     if group is not None:
@@ -83,7 +83,7 @@ def _knn_lists(words, emb, knn_queries, ctx, dev, group):
 def run(train, test, labels, words_all, emb_all, words_12, emb_12, n_items: int = config.N_ITEMS_OTTO,
         n_clusters: int = 50, kmeans_iter: int = 100, knn_queries: int = config.W2VEC_SEARCH_SIMILAR_FOR_FIRST_N_AIDS,
         ctx=None, timings: dict | None = None, keep_tables: bool = False, group=None, n_init="auto",
-        per_file: int | None = None, keep_candidates: bool = True) -> dict:
+        per_file: int | None = None, keep_candidates: bool = True, knn_exact: bool = False) -> dict:
     """Config 5 end to end. group (torch.distributed, one process per GPU): train and test files
     are dealt whole to ranks (count + sharded A6 per folder, replicated A7 and R1), kNN queries are
     split over ranks and all-gathered, KMeans rows (every session) are sharded with all-reduced
@@ -91,7 +91,8 @@ def run(train, test, labels, words_all, emb_all, words_12, emb_12, n_items: int 
     files; recall sums are all-reduced. Every rank returns the global numbers; 'candidates' is the
     whole job's candidate count and 'local_candidates' this rank's. keep_tables: host copies of every
     stage's output in 'intermediates' (the candidates as a DataFrame, or with keep_candidates=False
-    as the device CSR 'candidates_csr' plus 'test_session_ids', for full-size runs)."""
+    as the device CSR 'candidates_csr' plus 'test_session_ids', for full-size runs). knn_exact: both kNN stages
+    run the exact search on centred indexes (w2vec.KnnIndex.search(exact=True))."""
     t_entry = time.perf_counter()
     import torch
     from .synth import file_session_bounds
@@ -186,7 +187,7 @@ def run(train, test, labels, words_all, emb_all, words_12, emb_12, n_items: int 
             tables[n] = (a, b, c)
         t = mark("R1", t)
     # ---- kNN of both Word2Vec models (model/retrieve.py:683-687)
-    knn = [_knn_lists(w, e, knn_queries, ctx, dev, group) for w, e in ((words_all, emb_all), (words_12, emb_12))]
+    knn = [_knn_lists(w, e, knn_queries, ctx, dev, group, knn_exact) for w, e in ((words_all, emb_all), (words_12, emb_12))]
     t = mark("knn", t)
     # ---- pop-cluster source: C1 embeddings of all sessions, C2 KMeans, C3 ranks (cl50)
     rmap_all = gp.row_of_aid_map(words_all, n_items, dev)  # aid -> row of emb_all, for C1 and R7

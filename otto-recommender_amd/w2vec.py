@@ -10,6 +10,12 @@ within the bf16 scores' error of it (DESIGN.md §5 kNN states the bound and the 
 an exact search: embeddings centred near the origin, not tightly clustered). The reference's faiss
 IVFFlat (nlist 100, nprobe 3) probes 3 of 100 lists. Word2Vec training (gensim) is out of
 scope: embeddings are an input (a vocabulary `words` in index_to_key order + vectors).
+
+That default search is exact inside the envelope only. `exact=True` (KnnIndex.search and every function
+below) is exact for every input: the index is packed centred (`center=True`), the main pass keeps every row
+within a derived margin of the running 24th-best score, all of them that can be among the top k are reranked
+in fp32, and a query with more than 512 such rows is answered by an fp32 scan of all rows (DESIGN.md §5 kNN,
+"Exact mode"). It costs time only where the data is hostile; `KnnIndex.last_exact_stats` says how often.
 """
 from __future__ import annotations
 
@@ -23,9 +29,11 @@ from . import config
 
 
 class KnnIndex:
-    """Device index over item embeddings (fp32 [V, dim] kept resident + packed bf16 operand)."""
+    """Device index over item embeddings (fp32 [V, dim] kept resident + packed bf16 operand).
+    center=True packs the rows minus their column mean (the operand of the exact search; distances and the
+    default search's results on centred data do not depend on it)."""
 
-    def __init__(self, embeddings, ctx=None, stream=None):
+    def __init__(self, embeddings, ctx=None, stream=None, center: bool = False):
         import torch
         _lib.require_gpu()
         self.ctx = ctx or _lib.context()
@@ -34,8 +42,15 @@ class KnnIndex:
         self.emb = emb.to(dev, torch.float32).contiguous()
         self.n_items, self.dim = (int(x) for x in self.emb.shape)
         self.h = ctypes.c_void_p()
-        _lib.check(_lib.load().ottohip_knn_index_create(self.ctx.h, _lib.ptr(self.emb), self.n_items, self.dim,
-                                                        ctypes.byref(self.h), _lib.stream_handle(stream)))
+        self.center = bool(center)
+        self.last_exact_stats = None
+        lib = _lib.load()
+        if center:
+            _lib.check(lib.ottohip_knn_index_create_ex(self.ctx.h, _lib.ptr(self.emb), self.n_items, self.dim,
+                                                       _lib.KNN_CENTER, ctypes.byref(self.h), _lib.stream_handle(stream)))
+        else:
+            _lib.check(lib.ottohip_knn_index_create(self.ctx.h, _lib.ptr(self.emb), self.n_items, self.dim,
+                                                    ctypes.byref(self.h), _lib.stream_handle(stream)))
 
     def free(self):
         if self.h:
@@ -48,11 +63,13 @@ class KnnIndex:
         except Exception:
             pass
 
-    def search(self, query_rows=None, n_q=None, k: int = 20, stream=None):
+    def search(self, query_rows=None, n_q=None, k: int = 20, stream=None, exact: bool = False):
         """k nearest rows per query row in ascending fp32 squared L2, ties by row index: returns torch
         (idx:int32 [n_q, k], d2:float32 [n_q, k]) on the device; slots past the index size are -1 / inf.
         The rows are the best k of 24 candidates chosen by bf16 scores (module docstring), so "ties by row
-        index" holds among at most 24 equal-score candidates: of more identical rows, some k come back."""
+        index" holds among at most 24 equal-score candidates: of more identical rows, some k come back.
+        exact=True: the exact search (module docstring): the same outputs for every input, ties by row index
+        among all equal rows; self.last_exact_stats = {"n_overflow", "max_appends", "sum_appends"} of the call."""
         import torch
         dev = self.emb.device
         if query_rows is None:
@@ -63,14 +80,22 @@ class KnnIndex:
             n = int(qr.numel())
         idx = torch.empty((n, k), dtype=torch.int32, device=dev)
         d2 = torch.empty((n, k), dtype=torch.float32, device=dev)
+        if exact:
+            st = _lib.KnnExactStats()
+            _lib.check(_lib.load().ottohip_knn_topk_exact(self.ctx.h, self.h, _lib.ptr(qr), n, k, _lib.ptr(idx),
+                                                          _lib.ptr(d2), ctypes.byref(st), _lib.stream_handle(stream)))
+            self.last_exact_stats = {"n_overflow": int(st.n_overflow), "max_appends": int(st.max_appends),
+                                     "sum_appends": int(st.sum_appends)}
+            return idx, d2
         _lib.check(_lib.load().ottohip_knn_topk(self.ctx.h, self.h, _lib.ptr(qr), n, k, _lib.ptr(idx), _lib.ptr(d2),
                                                 _lib.stream_handle(stream)))
         return idx, d2
 
 
-def load_index_faiss_ivff(embeddings, model_name: str | None = None) -> KnnIndex:
-    """w2vec_aids.py:98-110 (the nlist/nprobe of config.W2VEC_MODELS do not apply: every row is scanned)."""
-    return KnnIndex(embeddings)
+def load_index_faiss_ivff(embeddings, model_name: str | None = None, exact: bool = False) -> KnnIndex:
+    """w2vec_aids.py:98-110 (the nlist/nprobe of config.W2VEC_MODELS do not apply: every row is scanned).
+    exact=True: a centred index, the operand of the exact search."""
+    return KnnIndex(embeddings, center=exact)
 
 
 def word_rows(words, words_q) -> np.ndarray:
@@ -91,13 +116,14 @@ def word_rows(words, words_q) -> np.ndarray:
 
 
 def get_top_k_similar_faiss(words_q, words, map_word_embedding=None, index_faiss_ivff=None, k: int = 20,
-                            return_itself: bool = True):
+                            return_itself: bool = True, exact: bool = False):
     """w2vec_aids.py:125-173. words_q: query aids; words: the vocabulary (row order of the
     index); index_faiss_ivff: a KnnIndex over embeddings in `words` order (map_word_embedding
     is accepted for signature compatibility; rows come from `words`). Words without an
     embedding are dropped as in :156-163. Returns pandas DataFrame
     [aid:int32, aid_next:int32, dist_w2vec:int32, rank_w2vec:int8] (dist_w2vec = trunc of the
-    squared L2 distance, :169; rank_w2vec = ordinal position 1..k clipped at 127, :170-171)."""
+    squared L2 distance, :169; rank_w2vec = ordinal position 1..k clipped at 127, :170-171).
+    exact=True: the exact search on the given index (best built with load_index_faiss_ivff(exact=True))."""
     import pandas as pd
     import torch
     index = index_faiss_ivff
@@ -111,18 +137,20 @@ def get_top_k_similar_faiss(words_q, words, map_word_embedding=None, index_faiss
     if len(rows) == 0:
         return pd.DataFrame({"aid": np.zeros(0, np.int32), "aid_next": np.zeros(0, np.int32),
                              "dist_w2vec": np.zeros(0, np.int32), "rank_w2vec": np.zeros(0, np.int8)})
-    res = knn_table(index, torch.from_numpy(words.astype(np.int32)), torch.from_numpy(rows.astype(np.int32)), k)
+    res = knn_table(index, torch.from_numpy(words.astype(np.int32)), torch.from_numpy(rows.astype(np.int32)), k,
+                    exact=exact)
     return pd.DataFrame({c: t.cpu().numpy() for c, t in res.items()})
 
 
-def knn_table(index: KnnIndex, words, query_rows, k: int = 20, stream=None) -> dict:
+def knn_table(index: KnnIndex, words, query_rows, k: int = 20, stream=None, exact: bool = False) -> dict:
     """Device form of the output of :167-171 for query rows: dict of torch columns
-    aid, aid_next (int32), dist_w2vec (int32, truncated squared L2), rank_w2vec (int8)."""
+    aid, aid_next (int32), dist_w2vec (int32, truncated squared L2), rank_w2vec (int8).
+    exact=True: the rows of the exact search (KnnIndex.search)."""
     import torch
     dev = index.emb.device
     words = torch.as_tensor(words).to(dev, torch.int32)
     qr = torch.as_tensor(query_rows).to(dev, torch.int32)
-    idx, d2 = index.search(qr, k=k, stream=stream)
+    idx, d2 = index.search(qr, k=k, stream=stream, exact=exact)
     n = qr.numel()
     valid = idx >= 0
     aid = words[qr.long()].view(n, 1).expand(n, k)
@@ -135,19 +163,20 @@ def knn_table(index: KnnIndex, words, query_rows, k: int = 20, stream=None) -> d
 
 
 def retrieve_w2vec_knns_via_faiss_index(embeddings, words, k: int | None = None, first_n_aids: int | None = None,
-                                        cache_file: str | None = None):
+                                        cache_file: str | None = None, exact: bool = False):
     """w2vec_aids.py:176-206 with the trained model replaced by its outputs (vocabulary `words`
     in index_to_key order and `embeddings`): neighbours of the first `first_n_aids` words,
-    cached to parquet like :191-204."""
+    cached to parquet like :191-204. exact=True: a centred index and the exact search."""
     import pandas as pd
     k = config.W2VEC_K if k is None else k
     first_n_aids = config.W2VEC_SEARCH_SIMILAR_FOR_FIRST_N_AIDS if first_n_aids is None else first_n_aids
     if cache_file and os.path.exists(cache_file):
         return pd.read_parquet(cache_file)
-    index = KnnIndex(embeddings)
+    index = KnnIndex(embeddings, center=exact)
     n_q = min(first_n_aids, index.n_items)
     import torch
-    res = knn_table(index, torch.as_tensor(np.asarray(words, np.int32)), torch.arange(n_q, dtype=torch.int32), k)
+    res = knn_table(index, torch.as_tensor(np.asarray(words, np.int32)), torch.arange(n_q, dtype=torch.int32), k,
+                    exact=exact)
     df = pd.DataFrame({c: t.cpu().numpy() for c, t in res.items()})
     index.free()
     if cache_file:
