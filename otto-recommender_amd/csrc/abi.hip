@@ -309,6 +309,75 @@ static int owner_map(ottohip_ctx* ctx, int32_t n_items, int G, hipStream_t s, co
   return 0;
 }
 
+// S3 of the fused layout without the sort's later passes (covis_kernels.h, "bucketed LDS counting sort"): (rks, poss)
+// = radix_skip_pass' output, En entries bucketed by the key's low byte from dstart / ntl on; (rkA, posA) = the idle
+// pair. Sets F.P, F.Rn, F.row_key, F.row_begin and F.poff32 (the reps' offsets: k_link_fix is the caller's) and
+// *taken; *taken stays false, with nothing of F written, when the rows hold 2^32 words or more (the per-key u32
+// totals may have wrapped, and the offsets need 64 bits): the caller finishes the sort instead.
+// The offsets leave the rank pass in entry order and k_poff_scatter_lds writes them in event order. The two outlets it
+// was measured against stay as A/B switches, read per call: OTTOHIP_ROWS_PART=1, the partition pass + k_poff_scatter
+// of the sort path; OTTOHIP_ROWS_DIRECT=1, the rank pass scatters to poff32 itself.
+constexpr int64_t RB_MIN_ENTRIES = 1024;
+static int rows_bucket(ottohip_ctx* ctx, Front& F, hipStream_t s, uint32_t* rks, uint32_t* poss, uint32_t* rkA,
+                       uint32_t* posA, int64_t E, int64_t En, const uint64_t* dstart, int ntl, uint32_t kmask,
+                       uint32_t INV, int cshift, const int* err, bool* taken) {
+  *taken = false;
+  Workspace& ws = ctx->ws;
+  const int nhi = (int)ceil_div((int64_t)INV, 256);  // keys < INV
+  if (nhi > RB_HI) { set_error("rows_bucket: %d key rows > %d", nhi, RB_HI); return OTTOHIP_EINVAL; }
+  const int64_t nk = (int64_t)nhi * 256;
+  const uint32_t* csrc = F.link ? F.link : F.cnt;
+  uint64_t *sums, *x, *xs;
+  uint32_t* btot;
+  OH_TRY(ws.get("rb_sums", 257, &sums));  // [256]: the scan's total
+  OH_TRY(ws.get("rb_tot", (size_t)nk, &btot));
+  OH_TRY(ws.get("rb_x", (size_t)nk, &x));
+  OH_TRY(ws.get("rb_xs", (size_t)nk, &xs));
+  const unsigned ntile = (unsigned)ceil_div(nhi, RB_TH);
+  k_rows_bucket_count<<<256, RB_T, 0, s>>>(rks, poss, csrc, En, dstart, ntl, kmask, cshift, nhi, btot, sums);
+  k_rows_bucket_keys<<<ntile, 256, 0, s>>>(btot, nhi, x);
+  OH_HIP(hipGetLastError());
+  OH_TRY(exclusive_scan_u64(ctx, x, xs, nk, sums + 256, s));
+  std::vector<uint64_t> h(257);
+  OH_TRY(d2h(h.data(), sums, 257, s));
+  int herr = 0;
+  OH_TRY(d2h(&herr, err, 1, s));
+  if (herr) { set_error("input out of range: aid outside [0, n_items) or type outside {0,1,2}"); return OTTOHIP_ERANGE; }
+  uint64_t words = 0;
+  for (int d = 0; d < 256; ++d) words += h[d];
+  if (words >= (1ull << 32)) return 0;
+  const uint64_t X = h[256];
+  F.P = X >> 24;
+  F.Rn = (int64_t)(X & 0xFFFFFFull);
+  OH_TRY(ws.get("row_key", (size_t)std::max<int64_t>(F.Rn, 1), &F.row_key));
+  OH_TRY(ws.get("row_begin", (size_t)std::max<int64_t>(F.Rn, 1), &F.row_begin));
+  F.poff = nullptr;
+  OH_TRY(ws.get("poff32", (size_t)E, &F.poff32));
+  uint32_t* wbase = btot;  // the totals are spent
+  k_rows_bucket_layout<<<ntile, 256, 0, s>>>(x, xs, nhi, F.row_key, F.row_begin, wbase);
+  // dstart stays the first pass' until the partition outlet's radix pass, after the rank pass
+  const char *denv = getenv("OTTOHIP_ROWS_DIRECT"), *penv = getenv("OTTOHIP_ROWS_PART");
+  if (denv && !strcmp(denv, "1")) {
+    k_rows_bucket_rank<true><<<256, RB_T, 0, s>>>(rks, poss, csrc, En, dstart, ntl, kmask, cshift, nhi, wbase, F.poff32,
+                                                  nullptr);
+  } else {
+    k_rows_bucket_rank<false><<<256, RB_T, 0, s>>>(rks, poss, csrc, En, dstart, ntl, kmask, cshift, nhi, wbase, nullptr,
+                                                   rkA);
+    if (penv && !strcmp(penv, "1")) {
+      OH_TRY(radix_pass(ctx, poss, rkA, posA, rks, En, std::max(0, bits_for((uint64_t)E) - 8), s));
+      k_poff_scatter<<<grid_for(En), 256, 0, s>>>(posA, rks, En, F.poff32);
+    } else {
+      constexpr int gt = PL_EV / RADIX_TILE_KEYS;
+      static_assert(gt >= 1, "an LDS image holds at least one sort tile of events");
+      k_poff_scatter_lds<<<(unsigned)ceil_div(ntl, gt), PL_T, 0, s>>>(poss, rkA, En, dstart, ntl, gt, RADIX_TILE_KEYS, E,
+                                                                    F.poff32);
+    }
+  }
+  OH_HIP(hipGetLastError());
+  *taken = true;
+  return 0;
+}
+
 // S1 prep, S2 count, S3 rows. n_parts > 1: owner-major rows, and (emit handle) owner bounds.
 static int covis_front(ottohip_ctx* ctx, const ottohip_events* ev, const ottohip_covis_params* params,
                        const int32_t* file_ids, int n_parts, Front& F, hipStream_t s, ottohip_emit* EM = nullptr) {
@@ -460,9 +529,32 @@ static int covis_front(ottohip_ctx* ctx, const ottohip_events* ev, const ottohip
   // the later passes and the row passes below run over the En kept entries
   int64_t En = E;
   const SortSkip skip{fused ? (1u << cshift) - 1u : 0u, INV, &En};
-  OH_TRY(radix_sort_pairs(ctx, rks, poss, rk2, pos2, E, kbits, s, fused, fused ? &skip : nullptr));
+  // bucketed rows (rows_bucket): one GPU, keys of at most 23 bits, u32 word offsets, more than a few entries;
+  // OTTOHIP_ROWS=sort (read per call, A/B switch) keeps the sort
+  const char* rows_env = getenv("OTTOHIP_ROWS");
+  const char* p32_env = getenv("OTTOHIP_POFF32");
+  bool bucketed = false;
+  if (fused && n_parts == 1 && kbits <= 23 && !(rows_env && !strcmp(rows_env, "sort")) &&
+      !(p32_env && !strcmp(p32_env, "0"))) {
+    const uint64_t* dstart = nullptr;
+    int ntl = 0;
+    OH_TRY(radix_skip_pass(ctx, rk, rk2, pos2, E, s, skip, &dstart, &ntl));
+    rks = rk2; poss = pos2;
+    if (En > RB_MIN_ENTRIES)
+      OH_TRY(rows_bucket(ctx, F, s, rk2, pos2, rk, pos, E, En, dstart, ntl, kmask, INV, cshift, err, &bucketed));
+    // not taken (few entries, or 2^32 words or more): the sort's remaining passes
+    if (!bucketed) OH_TRY(radix_sort_pairs(ctx, rks, poss, rk, pos, En, kbits, s, false, nullptr, 8));
+  } else {
+    OH_TRY(radix_sort_pairs(ctx, rks, poss, rk2, pos2, E, kbits, s, fused, fused ? &skip : nullptr));
+  }
   uint64_t* tot;
   OH_TRY(ws.get("tot", 4, &tot));
+  if (bucketed) {
+    if (F.link) k_link_fix<<<grid_for(E, 256 * LF_PER), 256, 0, s>>>(F.link, E, F.poff32, F.poff);
+    OH_HIP(hipGetLastError());
+    ctx->end(ph, s);
+    return 0;
+  }
   if (fused) {
     // saturated count bytes are read back from the link array (grouped: the group's total) or the counts
     const uint32_t* csrc = F.link ? F.link : F.cnt;

@@ -899,6 +899,205 @@ __global__ __launch_bounds__(256) void k_poff_scatter_xcd(const uint32_t* __rest
   }
 }
 
+// ---- bucketed LDS counting sort of the row entries (fused layout, one GPU, keys of at most 23 bits). The sort's
+// compacting first pass leaves bucket d = key & 255 with every kept entry of that low byte, so a bucket's keys differ
+// only in hi = key >> 8 < 2^15: one workgroup per bucket keeps one u32 per hi in LDS. k_rows_bucket_count adds the
+// entries' pair counts per key, k_rows_bucket_keys turns the totals into key order as X = count << 24 | [count != 0]
+// (the u64 scan of X carries word offset and row index, as in k_rows_tile), k_rows_bucket_layout writes the rows and
+// every key's first word, and k_rows_bucket_rank hands each entry its run by one returning LDS atomic on its key's
+// cursor. No entry moves after the first pass. The order of the runs inside a row follows the order of the atomics
+// (it varies from run to run; the reduce sorts a row's words), row_key / row_begin are those of the sort path.
+constexpr int RB_T = 1024, RB_U = 8, RB_HI = 1 << 15, RB_TH = 32;
+
+// bucket d = the entries [dstart[d * ntiles], dstart[(d + 1) * ntiles]) (radix_skip_pass' digit starts), the last one to n
+__device__ __forceinline__ void rows_bucket_range(const uint64_t* __restrict__ dstart, int ntiles, int64_t n, int d,
+                                                  int64_t& a, int64_t& b) {
+  a = (int64_t)dstart[(int64_t)d * ntiles];
+  b = d + 1 < 256 ? (int64_t)dstart[(int64_t)(d + 1) * ntiles] : n;
+}
+
+// an entry's pair count (rows_x) and hi; entries whose hi is outside the table (an out-of-range aid or type, reported
+// through err by S1) count nothing
+__device__ __forceinline__ uint32_t rows_bucket_entry(uint32_t kk, const uint32_t* __restrict__ poss,
+                                                      const uint32_t* __restrict__ cnt, int64_t k, uint32_t kmask,
+                                                      int shift, int nhi, uint32_t& hi) {
+  hi = (kk & kmask) >> 8;
+  if (hi >= (uint32_t)nhi) { hi = 0; return 0u; }
+  uint32_t c = kk >> shift;
+  if (c == RK_CSAT) c = cnt[poss[k]] & ~LK_REP;
+  return c;
+}
+
+// grid 256 (one bucket each): btot[d * nhi + hi] = the words of key hi << 8 | d (mod 2^32), bsum[d] = the bucket's words
+__global__ __launch_bounds__(RB_T) void k_rows_bucket_count(const uint32_t* __restrict__ rks,
+                                                            const uint32_t* __restrict__ poss,
+                                                            const uint32_t* __restrict__ cnt, int64_t n,
+                                                            const uint64_t* __restrict__ dstart, int ntiles,
+                                                            uint32_t kmask, int shift, int nhi,
+                                                            uint32_t* __restrict__ btot,
+                                                            uint64_t* __restrict__ bsum) {
+  __shared__ uint32_t tab[RB_HI];
+  __shared__ uint64_t ws[RB_T / 64];
+  const int d = blockIdx.x;
+  for (int i = threadIdx.x; i < nhi; i += RB_T) tab[i] = 0u;
+  __syncthreads();
+  int64_t a, b;
+  rows_bucket_range(dstart, ntiles, n, d, a, b);
+  uint64_t s = 0;
+  for (int64_t k0 = a + threadIdx.x; k0 < b; k0 += RB_T * RB_U) {
+    uint32_t kk[RB_U];
+#pragma unroll
+    for (int j = 0; j < RB_U; ++j) kk[j] = k0 + j * RB_T < b ? rks[k0 + j * RB_T] : 0u;
+#pragma unroll
+    for (int j = 0; j < RB_U; ++j) {
+      const int64_t k = k0 + j * RB_T;
+      if (k < b) {
+        uint32_t hi;
+        const uint32_t c = rows_bucket_entry(kk[j], poss, cnt, k, kmask, shift, nhi, hi);
+        if (c) atomicAdd(&tab[hi], c);
+        s += c;
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nhi; i += RB_T) btot[(int64_t)d * nhi + i] = tab[i];
+  s = wave_sum64(s);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t t = 0;
+    for (int w = 0; w < RB_T / 64; ++w) t += ws[w];
+    bsum[d] = t;
+  }
+}
+
+// btot (bucket-major) -> x[hi << 8 | d] = count << 24 | [count != 0] in key order, by tiles of RB_TH hi x 256 buckets
+// staged in LDS (128-B reads of each bucket's totals, 2-KB runs of keys written); grid ceil(nhi / RB_TH) x 256 threads
+__global__ __launch_bounds__(256) void k_rows_bucket_keys(const uint32_t* __restrict__ btot, int nhi,
+                                                          uint64_t* __restrict__ x) {
+  __shared__ uint32_t t[256][RB_TH + 1];
+  const int h0 = blockIdx.x * RB_TH, hl = threadIdx.x & (RB_TH - 1);
+  for (int d = threadIdx.x / RB_TH; d < 256; d += 256 / RB_TH)
+    t[d][hl] = h0 + hl < nhi ? btot[(int64_t)d * nhi + h0 + hl] : 0u;
+  __syncthreads();
+  for (int i = 0; i < RB_TH && h0 + i < nhi; ++i) {
+    const uint32_t c = t[threadIdx.x][i];
+    x[(int64_t)(h0 + i) * 256 + threadIdx.x] = ((uint64_t)c << 24) | (c ? 1u : 0u);
+  }
+}
+
+// xs = the exclusive scan of x: the rows (key, first word) of the keys with words, and every key's first word back in
+// bucket-major order for the rank pass (all word offsets < 2^32); same grid and tiles as k_rows_bucket_keys
+__global__ __launch_bounds__(256) void k_rows_bucket_layout(const uint64_t* __restrict__ x,
+                                                            const uint64_t* __restrict__ xs, int nhi,
+                                                            uint32_t* __restrict__ row_key,
+                                                            uint64_t* __restrict__ row_begin,
+                                                            uint32_t* __restrict__ wbase) {
+  __shared__ uint32_t t[256][RB_TH + 1];
+  const int h0 = blockIdx.x * RB_TH, hl = threadIdx.x & (RB_TH - 1);
+  for (int i = 0; i < RB_TH && h0 + i < nhi; ++i) {
+    const int64_t k = (int64_t)(h0 + i) * 256 + threadIdx.x;
+    const uint64_t v = xs[k];
+    if (x[k] & 1u) {
+      const uint64_t r = v & 0xFFFFFFull;
+      row_key[r] = (uint32_t)k;
+      row_begin[r] = v >> 24;
+    }
+    t[threadIdx.x][i] = (uint32_t)(v >> 24);
+  }
+  __syncthreads();
+  if (h0 + hl < nhi)
+    for (int d = threadIdx.x / RB_TH; d < 256; d += 256 / RB_TH) wbase[(int64_t)d * nhi + h0 + hl] = t[d][hl];
+}
+
+// grid 256: every entry's word offset = its key's cursor before the entry's count was added. DIRECT: poff32[position]
+// = offset; else woff[k] = offset beside the entry (one radix pass on the positions and k_poff_scatter follow)
+template <bool DIRECT>
+__global__ __launch_bounds__(RB_T) void k_rows_bucket_rank(const uint32_t* __restrict__ rks,
+                                                           const uint32_t* __restrict__ poss,
+                                                           const uint32_t* __restrict__ cnt, int64_t n,
+                                                           const uint64_t* __restrict__ dstart, int ntiles,
+                                                           uint32_t kmask, int shift, int nhi,
+                                                           const uint32_t* __restrict__ wbase,
+                                                           uint32_t* __restrict__ poff32,
+                                                           uint32_t* __restrict__ woff) {
+  __shared__ uint32_t tab[RB_HI];
+  const int d = blockIdx.x;
+  for (int i = threadIdx.x; i < nhi; i += RB_T) tab[i] = wbase[(int64_t)d * nhi + i];
+  __syncthreads();
+  int64_t a, b;
+  rows_bucket_range(dstart, ntiles, n, d, a, b);
+  for (int64_t k0 = a + threadIdx.x; k0 < b; k0 += RB_T * RB_U) {
+    uint32_t kk[RB_U], ps[RB_U];
+#pragma unroll
+    for (int j = 0; j < RB_U; ++j) {
+      const bool in = k0 + j * RB_T < b;
+      kk[j] = in ? rks[k0 + j * RB_T] : 0u;
+      if constexpr (DIRECT) ps[j] = in ? poss[k0 + j * RB_T] : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < RB_U; ++j) {
+      const int64_t k = k0 + j * RB_T;
+      if (k < b) {
+        uint32_t hi;
+        const uint32_t c = rows_bucket_entry(kk[j], poss, cnt, k, kmask, shift, nhi, hi);
+        const uint32_t off = c ? atomicAdd(&tab[hi], c) : 0u;
+        if constexpr (DIRECT) poff32[ps[j]] = off;
+        else woff[k] = off;
+      }
+    }
+  }
+}
+
+// the offsets in event order straight from the buckets: a bucket's entries are in event order, and the first pass'
+// offsets (dstart[d * ntiles + t] = bucket d's first entry from the events of sort tile t on) cut all buckets at the
+// same events. Block g gathers the entries of all 256 buckets whose events lie in its gt sort tiles of tile_ev events
+// (gt * tile_ev <= PL_EV) into an LDS image of that slice of poff32 and writes the image linearly, so every line of
+// poff32 goes out once, whole (the events without an entry get 0: members are set by k_link_fix, the others are
+// never read). Measured at 220 M events against k_poff_scatter's 4-B writes after a partition pass: rows 6.8 -> 4.8 ms.
+constexpr int PL_T = 1024, PL_EV = 32768, PL_J = 4;
+__global__ __launch_bounds__(PL_T) void k_poff_scatter_lds(const uint32_t* __restrict__ pos,
+                                                           const uint32_t* __restrict__ woff, int64_t n,
+                                                           const uint64_t* __restrict__ dstart, int ntiles, int gt,
+                                                           int tile_ev, int64_t E, uint32_t* __restrict__ poff32) {
+  __shared__ uint32_t img[PL_EV];
+  const int t0 = blockIdx.x * gt, t1 = t0 + gt;
+  const int64_t p0 = (int64_t)t0 * tile_ev;
+  const uint32_t np = (uint32_t)(E - p0 < (int64_t)gt * tile_ev ? E - p0 : (int64_t)gt * tile_ev);
+  for (uint32_t i = threadIdx.x; i < np; i += PL_T) img[i] = 0u;
+  __syncthreads();
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  // wave w: buckets [w * 16, w * 16 + 16), PL_J at a time so that their loads are in flight together
+  for (int d0 = w * (256 / (PL_T / 64)); d0 < (w + 1) * (256 / (PL_T / 64)); d0 += PL_J) {
+    int64_t k[PL_J], b[PL_J];
+#pragma unroll
+    for (int j = 0; j < PL_J; ++j) {
+      const int d = d0 + j;
+      k[j] = (int64_t)dstart[(int64_t)d * ntiles + t0] + l;
+      b[j] = t1 < ntiles ? (int64_t)dstart[(int64_t)d * ntiles + t1]
+                         : (d + 1 < 256 ? (int64_t)dstart[(int64_t)(d + 1) * ntiles] : n);
+    }
+    bool more = true;
+    while (more) {
+      uint32_t p[PL_J], o[PL_J];
+#pragma unroll
+      for (int j = 0; j < PL_J; ++j) {
+        p[j] = k[j] < b[j] ? pos[k[j]] - (uint32_t)p0 : 0xFFFFFFFFu;
+        o[j] = k[j] < b[j] ? woff[k[j]] : 0u;
+      }
+      more = false;
+#pragma unroll
+      for (int j = 0; j < PL_J; ++j) {
+        if (p[j] < np) img[p[j]] = o[j];
+        k[j] += 64;
+        more |= k[j] - l < b[j];
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < np; i += PL_T) poff32[p0 + i] = img[i];
+}
+
 // ---- rows without a sort (OTTOHIP_ROWS=atomic, one GPU): the row of key k is the dense index k of
 // (type << A | aid); its words are cut into RA_SUB sub-ranges, one per counter, so the atomics of a hot
 // row spread over RA_SUB addresses. Each event takes its run inside its sub-range with one returning

@@ -17,8 +17,21 @@ struct SortSkip {
   uint32_t mask, inv;
   int64_t* n_out;
 };
+// shift0 (a multiple of 8, without skip): the passes start at this bit, for pairs already ordered by the bits below it
 int radix_sort_pairs(Ctx* ctx, uint32_t*& keys, uint32_t*& vals, uint32_t* keys_alt, uint32_t* vals_alt,
-                     int64_t n, int bits, hipStream_t s, bool iota_vals = false, const SortSkip* skip = nullptr);
+                     int64_t n, int bits, hipStream_t s, bool iota_vals = false, const SortSkip* skip = nullptr,
+                     int shift0 = 0);
+// the compacting first pass alone: keys[0, n) -> (kout, vout), the kept (key, index) pairs bucketed by key & 255 in
+// index order; *skip.n_out = the kept count (read back on the host). digit_start / n_tiles as in radix_pass: bucket d
+// starts at (*digit_start)[d * *n_tiles], valid until the next radix pass on ctx.
+// radix_sort_pairs(kout, vout, ..., shift0 = 8) over the kept pairs finishes the sort.
+int radix_skip_pass(Ctx* ctx, const uint32_t* keys, uint32_t* kout, uint32_t* vout, int64_t n, hipStream_t s,
+                    const SortSkip& skip, const uint64_t** digit_start = nullptr, int* n_tiles = nullptr);
+// keys per tile of a radix pass: column t of digit_start covers the input keys [t, t + 1) * RADIX_TILE_KEYS
+#ifndef OH_RS_R
+#define OH_RS_R 16  // keys per thread and sub-tile (A/B build flag)
+#endif
+constexpr int RADIX_TILE_KEYS = 256 * OH_RS_R * 4;
 // one stable 8-bit pass on digit (key >> shift) & 255
 int radix_pass(Ctx* ctx, const uint32_t* kin, const uint32_t* vin, uint32_t* kout, uint32_t* vout, int64_t n,
                int shift, hipStream_t s, const uint64_t** digit_start = nullptr, int* n_tiles = nullptr);

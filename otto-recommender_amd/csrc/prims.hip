@@ -95,13 +95,11 @@ int exclusive_scan_u64(Ctx* ctx, const uint64_t* in, uint64_t* out, int64_t n, u
 }
 
 // ------------------------------------------------------------------ radix sort
-#ifndef OH_RS_R
-#define OH_RS_R 16
-#endif
 constexpr int RS_T = 256, RS_WAVES = RS_T / 64, RS_R = OH_RS_R, RS_TILE = RS_T * RS_R;  // 4096 (keys per thread: A/B build flag)
 // a block sorts RS_SUB consecutive tiles in order, so the digit-count matrix (and its scan) has one
 // column per 4 tiles: the scan of every pass was larger than the scatter's own work
 constexpr int RS_SUB = 4, RS_BLOCK = RS_TILE * RS_SUB;
+static_assert(RS_BLOCK == RADIX_TILE_KEYS, "prims.h: RADIX_TILE_KEYS");
 
 // Workgroups are dealt to the 8 XCDs round robin (block b -> XCD b % 8), each XCD with its own L2. With
 // xcd != 0 block b takes tile xcd_tile(b): XCD x sorts the x-th eighth of the tiles, so consecutive tiles,
@@ -260,42 +258,59 @@ int radix_pass(Ctx* ctx, const uint32_t* kin, const uint32_t* vin, uint32_t* kou
   return 0;
 }
 
+// the compacting first pass of radix_sort_pairs alone: generates the values (indices) and drops the skipped keys
+int radix_skip_pass(Ctx* ctx, const uint32_t* keys, uint32_t* kout, uint32_t* vout, int64_t n, hipStream_t s,
+                    const SortSkip& skip, const uint64_t** digit_start, int* n_tiles) {
+  *skip.n_out = 0;
+  if (n <= 0) return 0;
+  if (n >= ((int64_t)1 << 32)) { set_error("radix_skip_pass: n=%lld too large", (long long)n); return OTTOHIP_ELIMIT; }
+  const int nb = (int)ceil_div(n, RS_BLOCK);
+  uint32_t* hist; uint64_t* gofs; uint64_t* tot;
+  OH_TRY(ctx->ws.get("rs_hist", (size_t)nb * 256, &hist));
+  OH_TRY(ctx->ws.get("rs_gofs", (size_t)nb * 256, &gofs));
+  OH_TRY(ctx->ws.get("rs_total", 1, &tot));
+  k_rs_hist<true><<<nb, RS_T, 0, s>>>(keys, n, 0, hist, nb, rs_xcd(), skip.mask, skip.inv);
+  OH_HIP(hipGetLastError());
+  OH_TRY(exclusive_scan_u32(ctx, hist, gofs, (int64_t)nb * 256, tot, s));
+  k_rs_scatter<true><<<nb, RS_T, 0, s>>>(keys, nullptr, kout, vout, n, 0, gofs, nb, 1, rs_xcd(), skip.mask, skip.inv);
+  OH_HIP(hipGetLastError());
+  uint64_t kept = 0;
+  OH_HIP(hipMemcpyAsync(&kept, tot, sizeof kept, hipMemcpyDeviceToHost, s));
+  OH_HIP(hipStreamSynchronize(s));
+  *skip.n_out = (int64_t)kept;
+  if (digit_start) *digit_start = gofs;
+  if (n_tiles) *n_tiles = nb;
+  return 0;
+}
+
 int radix_sort_pairs(Ctx* ctx, uint32_t*& keys, uint32_t*& vals, uint32_t* keys_alt, uint32_t* vals_alt,
-                     int64_t n, int bits, hipStream_t s, bool iota_vals, const SortSkip* skip) {
+                     int64_t n, int bits, hipStream_t s, bool iota_vals, const SortSkip* skip, int shift0) {
   if (skip) {  // the compacting first pass generates the values and drops the skipped keys
-    if (!iota_vals || bits <= 0) { set_error("radix_sort_pairs: skipping needs iota values and bits > 0"); return OTTOHIP_EINVAL; }
+    if (!iota_vals || bits <= 0 || shift0 != 0) {
+      set_error("radix_sort_pairs: skipping needs iota values, bits > 0 and all digits");
+      return OTTOHIP_EINVAL;
+    }
     *skip->n_out = 0;
     if (n <= 0) return 0;
-  } else if (n <= 1 || bits <= 0) {  // nothing to sort; generated values still have to be written
+    OH_TRY(radix_skip_pass(ctx, keys, keys_alt, vals_alt, n, s, *skip));
+    std::swap(keys, keys_alt); std::swap(vals, vals_alt);
+    n = *skip->n_out;
+    shift0 = 8;
+    iota_vals = false;
+  }
+  if (n <= 1 || bits <= shift0) {  // nothing (left) to sort; generated values still have to be written
     if (iota_vals && n > 1) { set_error("radix_sort_pairs: iota values need bits > 0"); return OTTOHIP_EINVAL; }
     if (iota_vals && n == 1) OH_HIP(hipMemsetAsync(vals, 0, sizeof(uint32_t), s));
     return 0;
   }
+  if (iota_vals && shift0 != 0) { set_error("radix_sort_pairs: iota values need the first digit"); return OTTOHIP_EINVAL; }
   if (n >= ((int64_t)1 << 32)) { set_error("radix_sort_pairs: n=%lld too large", (long long)n); return OTTOHIP_ELIMIT; }
-  int nb = (int)ceil_div(n, RS_BLOCK);
+  const int nb = (int)ceil_div(n, RS_BLOCK);
   uint32_t* hist; uint64_t* gofs;
   OH_TRY(ctx->ws.get("rs_hist", (size_t)nb * 256, &hist));
   OH_TRY(ctx->ws.get("rs_gofs", (size_t)nb * 256, &gofs));
   uint32_t *ka = keys, *va = vals, *kb = keys_alt, *vb = vals_alt;
-  for (int shift = 0; shift < bits; shift += 8) {
-    if (skip && shift == 0) {
-      uint64_t* tot;
-      OH_TRY(ctx->ws.get("rs_total", 1, &tot));
-      k_rs_hist<true><<<nb, RS_T, 0, s>>>(ka, n, 0, hist, nb, rs_xcd(), skip->mask, skip->inv);
-      OH_HIP(hipGetLastError());
-      OH_TRY(exclusive_scan_u32(ctx, hist, gofs, (int64_t)nb * 256, tot, s));
-      k_rs_scatter<true><<<nb, RS_T, 0, s>>>(ka, va, kb, vb, n, 0, gofs, nb, 1, rs_xcd(), skip->mask, skip->inv);
-      OH_HIP(hipGetLastError());
-      uint64_t kept = 0;
-      OH_HIP(hipMemcpyAsync(&kept, tot, sizeof kept, hipMemcpyDeviceToHost, s));
-      OH_HIP(hipStreamSynchronize(s));
-      n = (int64_t)kept;
-      *skip->n_out = n;
-      nb = (int)ceil_div(n, RS_BLOCK);
-      std::swap(ka, kb); std::swap(va, vb);
-      if (n <= 1) break;  // nothing left to order: (ka, va) hold the kept key, if any
-      continue;
-    }
+  for (int shift = shift0; shift < bits; shift += 8) {
     k_rs_hist<<<nb, RS_T, 0, s>>>(ka, n, shift, hist, nb, rs_xcd());
     OH_HIP(hipGetLastError());
     OH_TRY(exclusive_scan_u32(ctx, hist, gofs, (int64_t)nb * 256, nullptr, s));
