@@ -315,6 +315,40 @@ int ottohip_labels_csr(ottohip_ctx* ctx, const int32_t* session_ids, int64_t n_s
 int ottohip_candidates_recall(ottohip_ctx* ctx, const ottohip_candidates* c, const int64_t* lab_off,
                               const int32_t* lab_aid, uint32_t src_mask, int max_k, int64_t* sums_out, void* stream);
 
+/* ---- Ranker feature columns of retrieve_and_gen_feats (model/retrieve.py:293-403, 522-602) ----
+ * Value columns aligned entry for entry with the lists of ottohip_cand_lists (same stable key order):
+ * q = 0..4 the R1 columns of the five co-count rules, dist[0..1] the kNN distances of q = 5, 6,
+ * pop_ranks6 [n_pop][6] the six cl50 ranks aligned with pop_aid (clicks, carts, orders, clicks_7d,
+ * carts_7d, orders_7d), cl1_ranks3 [n_items][3] the cl1 ranks by aid (-1 = the aid has no row) or NULL.
+ * A pointer of an absent source (off[q] == NULL) is ignored. */
+typedef struct {
+  const int32_t* count[5];
+  const int16_t* count_pop[5];
+  const int16_t* perc_pop[5];
+  const int8_t* count_rel[5];
+  const int32_t* dist[2];
+  const int16_t* pop_ranks6;
+  const int16_t* cl1_ranks3;
+} ottohip_feat_values;
+/* The ordered column table of the feature frame, no GPU call: returns the number of columns n; for
+ * 0 <= i < n also *name (static string) and *dtype (0 int8, 1 int16, 2 int32, 3 float32). The last three
+ * columns are the targets. Semantics of every column: DESIGN.md (feature columns). */
+int ottohip_feature_columns(int i, const char** name, int* dtype);
+/* The feature columns of the candidates of sessions [s_lo, s_hi) of a handle made by
+ * ottohip_candidates_generate from the same event CSR, lists and session_cl. cols[n_cols] (host array of
+ * device pointers, order of ottohip_feature_columns; n_cols = its n, or n - 3 without targets): column i
+ * receives off[s_hi] - off[s_lo] values in the handle's candidate order; a NULL entry skips the column.
+ * "session" receives the session's index in the handle. cos_sim_ses_aid / eucl_dist_ses_aid are not
+ * written: they are ottohip_session_item_similarity's outputs over the same range. lab_off / lab_aid:
+ * the ottohip_labels_csr layout over the handle's sessions, or NULL (targets written as 0).
+ * OTTOHIP_ELIMIT: a session of the range has more than 512 events, an aid more than 256 list entries, or
+ * a finished value does not fit its column's dtype (a {rule}_count sum above 2^31 - 1). */
+int ottohip_candidates_features(ottohip_ctx* ctx, const ottohip_candidates* c, const int64_t* session_offsets,
+                                const int32_t* aid, const int32_t* ts, const int8_t* type,
+                                const ottohip_cand_lists* lists, const ottohip_feat_values* values,
+                                const int32_t* session_cl, const int64_t* lab_off, const int32_t* lab_aid,
+                                int64_t s_lo, int64_t s_hi, void* const* cols, int n_cols, void* stream);
+
 /* ---- Pop-cluster source (C1-C3) and session-item similarity (R7) -------------------------
  * C1 compute_sessions_embeddings (model/kmeans_sessions.py:40-86): per session
  *    round6(sum w e_aid / sum w), w = f32(max(0.1, 1 - (max_ts - ts)/259200) * {0.1,0.3,0.6}[type]);

@@ -115,6 +115,10 @@ SIGNATURES = {
     "ottohip_labels_csr": (ctypes.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _I64, _VP, _VP, ctypes.POINTER(_I64), _VP]),
     "ottohip_candidates_recall": (ctypes.c_int, [_VP, _VP, _VP, _VP, ctypes.c_uint32, ctypes.c_int,
                                                  ctypes.POINTER(_I64), _VP]),
+    "ottohip_feature_columns": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p),
+                                               ctypes.POINTER(ctypes.c_int)]),
+    "ottohip_candidates_features": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I64,
+                                                   _VP, ctypes.c_int, _VP]),
     "ottohip_session_embeddings": (ctypes.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _I32, _VP, ctypes.c_int, _VP, _VP]),
     "ottohip_kmeans_step": (ctypes.c_int, [_VP, _VP, _I64, ctypes.c_int, _VP, ctypes.c_int, _VP,
                                            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _VP]),

@@ -90,6 +90,85 @@ class CandidateSources:
             self.abi.n_clusters = 0
 
 
+CL50_RANKS = ["rank_clicks_cl50", "rank_carts_cl50", "rank_orders_cl50", "rank_clicks_7d_cl50",
+              "rank_carts_7d_cl50", "rank_orders_7d_cl50"]
+CL1_RANKS = ["rank_clicks_cl1", "rank_carts_cl1", "rank_orders_cl1"]
+_FEAT_NP = {0: np.int8, 1: np.int16, 2: np.int32, 3: np.float32}
+
+
+def feature_columns(with_targets: bool = True) -> list:
+    """ottohip_feature_columns (no GPU call): [(name, numpy dtype)] of the feature frame in file order."""
+    lib = _lib.load()
+    n = lib.ottohip_feature_columns(-1, None, None)
+    out = []
+    for i in range(n):
+        nm, dt = ctypes.c_char_p(), ctypes.c_int()
+        lib.ottohip_feature_columns(i, ctypes.byref(nm), ctypes.byref(dt))
+        out.append((nm.value.decode(), np.dtype(_FEAT_NP[dt.value])))
+    return out if with_targets else [c for c in out if not c[0].startswith("target_")]
+
+
+class FeatValues(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_void_p * 5), ("count_pop", ctypes.c_void_p * 5), ("perc_pop", ctypes.c_void_p * 5),
+                ("count_rel", ctypes.c_void_p * 5), ("dist", ctypes.c_void_p * 2), ("pop_ranks6", ctypes.c_void_p),
+                ("cl1_ranks3", ctypes.c_void_p)]
+
+
+def list_order(key, n_keys: int, ctx=None):
+    """The row permutation build_lists applies (stable by key): row i of the CSR is input row perm[i]."""
+    import torch
+    n = len(key)
+    _, perm, _ = build_lists(key, torch.arange(n, dtype=torch.int32), None, n_keys, ctx)
+    return perm[:n].long()
+
+
+class FeatureValues:
+    """Value columns aligned entry for entry with the lists of a CandidateSources (ottohip_feat_values), rows given
+    in the same order as the rows the sources were built from.
+    r1: {rule: (aid, count, count_pop, perc_pop, count_rel)}; knn_all / knn_12: (aid, dist);
+    pop: (cluster index, ranks6 [n, 6]) for the rows of the sources' pop lists; cl1: (aid, ranks3 [n, 3]) or None."""
+
+    def __init__(self, sources: CandidateSources, r1: dict, knn_all, knn_12, pop=None, cl1=None):
+        import torch
+        self.ctx = sources.ctx
+        dev = _dev(self.ctx)
+        self.keep = []
+        self.abi = FeatValues()
+
+        def put(vals, perm, dt):
+            v = (vals if isinstance(vals, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(vals))).to(dev, dt)
+            v = v[perm].contiguous() if v.numel() else torch.zeros(1, dtype=dt, device=dev)
+            self.keep.append(v)
+            return _lib.ptr(v)
+
+        for q, n in enumerate(config.CO_EVENTS_TO_COUNT):
+            src = r1.get(n)
+            if src is None:
+                continue
+            a, c, cp, pp, cr = src
+            perm = list_order(a, sources.n_items, self.ctx)
+            self.abi.count[q] = put(c, perm, torch.int32)
+            self.abi.count_pop[q] = put(cp, perm, torch.int16)
+            self.abi.perc_pop[q] = put(pp, perm, torch.int16)
+            self.abi.count_rel[q] = put(cr, perm, torch.int8)
+        for w, src in enumerate((knn_all, knn_12)):
+            if src is None:
+                continue
+            a, d = src
+            self.abi.dist[w] = put(d, list_order(a, sources.n_items, self.ctx), torch.int32)
+        if pop is not None and sources.n_clusters > 0:
+            c, r6 = pop
+            self.abi.pop_ranks6 = put(np.asarray(r6).reshape(-1, 6), list_order(c, sources.n_clusters, self.ctx),
+                                      torch.int16)
+        if cl1 is not None:
+            a, r3 = cl1
+            dense = np.full((sources.n_items, 3), -1, np.int16)
+            dense[np.asarray(a, np.int64)] = np.asarray(r3, np.int16).reshape(-1, 3)
+            t = torch.from_numpy(dense).to(dev)
+            self.keep.append(t)
+            self.abi.cl1_ranks3 = _lib.ptr(t)
+
+
 class Candidates:
     """Device CSR of candidates per session: off [S+1], aid_next, ts_order_aid, flags."""
 
@@ -129,6 +208,50 @@ class Candidates:
         p = [ctypes.c_void_p() for _ in range(4)]
         _lib.check(_lib.load().ottohip_candidates_view(self.h, *(ctypes.byref(x) for x in p)))
         return {k: int(x.value or 0) for k, x in zip(("off", "aid_next", "ts_order_aid", "flags"), p)}
+
+    def features(self, events, sources: CandidateSources, values: FeatureValues, session_cl=None, labels=None,
+                 lo: int = 0, hi: int | None = None, stream=None) -> dict:
+        """ottohip_candidates_features for the sessions [lo, hi): {column name: torch tensor} in the order of
+        feature_columns(), one value per candidate of the range in the handle's order. events = (offsets, aid, ts,
+        type), sources and session_cl are those the handle was generated from (device tensors are used in place);
+        labels = (lab_off, lab_aid) in the labels_csr layout, None omits the target columns. "session" holds the
+        session's index in the handle; cos_sim_ses_aid / eucl_dist_ses_aid hold their null fills (0, -1): they are
+        popularity.session_item_similarity's outputs over the same range."""
+        import torch
+        dev = _dev(self.ctx)
+        hi = self.n_sessions if hi is None else int(hi)
+        lo = int(lo)
+        if not (0 <= lo <= hi <= self.n_sessions):
+            raise ValueError(f"session range [{lo}, {hi}) outside [0, {self.n_sessions}]")
+        t = lambda x, d: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(dev, d).contiguous()
+        off, a, s_, y = (t(events[0], torch.int64), t(events[1], torch.int32), t(events[2], torch.int32),
+                         t(events[3], torch.int8))
+        if off.numel() and int(off[0].item()) != 0:
+            off = off - off[0]
+        cl = None if session_cl is None else t(session_cl, torch.int32)
+        lab = None if labels is None else (t(labels[0], torch.int64), t(labels[1], torch.int32))
+        coff = getattr(self, "_off_host", None)
+        if coff is None:
+            coff = self._off_host = self.to_torch()["off"].cpu().numpy()
+        n = int(coff[hi] - coff[lo])
+        table = feature_columns(labels is not None)
+        out, ptrs = {}, (ctypes.c_void_p * len(table))()
+        for i, (nm, dt) in enumerate(table):
+            tt = getattr(torch, dt.name)
+            if nm == "cos_sim_ses_aid":
+                out[nm] = torch.zeros(n, dtype=tt, device=dev)
+            elif nm == "eucl_dist_ses_aid":
+                out[nm] = torch.full((n,), -1.0, dtype=tt, device=dev)
+            else:
+                out[nm] = torch.empty(n, dtype=tt, device=dev)
+            ptrs[i] = _lib.ptr(out[nm]) if n else None
+        _lib.check(_lib.load().ottohip_candidates_features(
+            self.ctx.h, self.h, _lib.ptr(off), _lib.ptr(a) if a.numel() else None, _lib.ptr(s_) if a.numel() else None,
+            _lib.ptr(y) if a.numel() else None, ctypes.addressof(sources.abi), ctypes.addressof(values.abi),
+            _lib.ptr(cl) if cl is not None else None, _lib.ptr(lab[0]) if lab is not None else None,
+            _lib.ptr(lab[1]) if (lab is not None and lab[1].numel()) else None, lo, hi, ptrs, len(table),
+            _lib.stream_handle(stream)))
+        return out
 
     def to_pandas(self, session_ids=None):
         """DataFrame[session, aid_next:int32, ts_order_aid:int16, src_*:int8] in output order."""
@@ -276,6 +399,141 @@ def retrieve_candidates(df_sessions_aids_full, aid_pairs_co_events: dict, df_knn
     if file_out is not None:
         write_retrieved(out, file_out)
     return out
+
+
+class FeatureJob:
+    """The device state behind retrieve_and_gen_feats for one sessions file: the candidates of every session
+    (generate) and the sources, value columns, labels and embeddings their features are made of. range(lo, hi)
+    returns the finished columns of the sessions [lo, hi) (positions in session-id order), so a caller, or each
+    rank of several, takes the file in pieces that fit its memory. Frames as retrieve_and_gen_feats takes them."""
+
+    def __init__(self, df_sessions_aids_full, aid_pairs_co_events: dict, df_knns_w2vec_all, df_knns_w2vec_1_2,
+                 df_session_cl, df_pop_cl1, df_pop_cl50, df_aid_embeddings, df_session_embeddings, df_labels,
+                 n_items: int | None = None):
+        import torch
+        from . import popularity as gp
+        from .synth import events_from_columns
+        d = df_sessions_aids_full
+        ses = d["session"].to_numpy()
+        if len(ses) and np.any(np.diff(ses.astype(np.int64)) < 0):
+            d = d.iloc[np.argsort(ses, kind="stable")]
+        ev = events_from_columns(d["session"].to_numpy(), d["aid"].to_numpy(), d["ts"].to_numpy(), d["type"].to_numpy())
+        sess_ids = ev.session[ev.session_offsets[:-1]] if ev.n_sessions else np.zeros(0, np.int32)
+        mx = [int(ev.aid.max()) + 1 if len(ev.aid) else 1, int(df_pop_cl1["aid"].max()) + 1 if len(df_pop_cl1) else 1]
+        r1, r1v = {}, {}
+        for n, df in aid_pairs_co_events.items():
+            a = df["aid"].to_numpy()
+            r1[n] = (a, df["aid_next"].to_numpy(), df[f"{n}_rank"].to_numpy())
+            r1v[n] = (a, df[f"{n}_count"].to_numpy(), df[f"{n}_count_pop"].to_numpy(), df[f"{n}_perc_pop"].to_numpy(),
+                      df[f"{n}_count_rel"].to_numpy())
+            mx.append(int(df["aid"].max()) + 1 if len(df) else 1)
+
+        def knn(df):
+            rc = [c for c in df.columns if c.startswith("rank_w2vec")][0]
+            dc = [c for c in df.columns if c.startswith("dist_w2vec")][0]
+            mx.append(int(df["aid"].max()) + 1 if len(df) else 1)
+            return (df["aid"].to_numpy(), df["aid_next"].to_numpy(), df[rc].to_numpy()), (df["aid"].to_numpy(), df[dc].to_numpy())
+
+        (ka, kav), (k12, k12v) = knn(df_knns_w2vec_all), knn(df_knns_w2vec_1_2)
+        n_items = max(mx + [n_items or 0, config.N_ITEMS_OTTO])
+        p = df_pop_cl50[df_pop_cl50[CL50_RANKS].min(axis=1) <= 20]  # :581-582
+        clusters = np.unique(np.concatenate([p["cl50"].to_numpy(), df_session_cl["cl50"].dropna().to_numpy()]))
+        pc = np.searchsorted(clusters, p["cl50"].to_numpy())
+        scl = session_cluster_index(df_session_cl, clusters, sess_ids)
+        src = CandidateSources(r1, ka, k12, (pc, p["aid"].to_numpy()), len(clusters), n_items)
+        val = FeatureValues(src, r1v, kav, k12v, (pc, p[CL50_RANKS].to_numpy()),
+                            (df_pop_cl1["aid"].to_numpy(), df_pop_cl1[CL1_RANKS].to_numpy()))
+        dev = _dev(src.ctx)
+        events = tuple(torch.as_tensor(x).to(dev) for x in (ev.session_offsets, ev.aid, ev.ts, ev.type))
+        scl_d = torch.from_numpy(scl).to(dev)
+        c = generate(*events, src, scl_d)
+        labels = None
+        if df_labels is not None:
+            lo_, la_ = labels_csr(df_labels, sess_ids)
+            labels = (torch.from_numpy(lo_).to(dev), torch.from_numpy(la_).to(dev))
+        # R7 inputs: session embedding rows in session order, item embeddings by aid
+        dim_a = [x for x in df_aid_embeddings.columns if x.startswith("dim_")]
+        dim_s = [x for x in df_session_embeddings.columns if x.startswith("dim_")]
+        sim = None
+        if len(dim_a) and len(dim_a) == len(dim_s) and len(df_aid_embeddings):
+            se = np.zeros((ev.n_sessions, len(dim_s)), np.float32)
+            has = np.zeros(ev.n_sessions, np.uint8)
+            order = np.argsort(sess_ids, kind="stable")
+            ks = df_session_embeddings["session"].to_numpy().astype(np.int64)
+            j = np.searchsorted(sess_ids[order], ks)
+            ok = (j < ev.n_sessions) & (sess_ids[order][np.minimum(j, max(ev.n_sessions - 1, 0))] == ks)
+            se[order[j[ok]]] = df_session_embeddings[dim_s].to_numpy().astype(np.float32)[ok]
+            has[order[j[ok]]] = 1
+            words = df_aid_embeddings["aid"].to_numpy()
+            emb = torch.from_numpy(np.ascontiguousarray(df_aid_embeddings[dim_a].to_numpy().astype(np.float32))).to(dev)
+            sim = (torch.from_numpy(se).to(dev), torch.from_numpy(has).to(dev), emb,
+                   gp.row_of_aid_map(words, n_items, dev), words)
+        self.cands, self.events, self.sources, self.values, self.session_cl = c, events, src, val, scl_d
+        self.labels, self.sim, self.n_items, self.n_sessions = labels, sim, n_items, ev.n_sessions
+        self.table = feature_columns(labels is not None)
+        t = c.to_torch()
+        self.cand_off, self.cand_next = t["off"], t["aid_next"]
+        self.cand_off_host = t["off"].cpu().numpy()
+        self.session_ids = torch.from_numpy(np.ascontiguousarray(sess_ids).astype(np.int32)).to(dev)
+
+    def range(self, lo: int, hi: int) -> dict:
+        """{column: torch tensor} of the sessions [lo, hi): Candidates.features with the session ids filled in and
+        cos / eucl from ottohip_session_item_similarity over the same range."""
+        from . import popularity as gp
+        f = self.cands.features(self.events, self.sources, self.values, self.session_cl, self.labels, lo, hi)
+        if f["session"].numel():
+            f["session"] = self.session_ids[f["session"].long()]
+            if self.sim is not None:
+                se, has, emb, rmap, words = self.sim
+                co = self.cand_off_host
+                off_r = self.cand_off[lo:hi + 1] - self.cand_off[lo]
+                f["cos_sim_ses_aid"], f["eucl_dist_ses_aid"] = gp.session_item_similarity(
+                    off_r, self.cand_next[int(co[lo]):int(co[hi])], se[lo:hi], words, emb, sess_has=has[lo:hi],
+                    n_items=self.n_items, ctx=self.sources.ctx, rmap=rmap)
+        return f
+
+    def free(self):
+        self.cands.free()
+
+
+def retrieve_and_gen_feats(df_sessions_aids_full, aid_pairs_co_events: dict, df_knns_w2vec_all, df_knns_w2vec_1_2,
+                           df_session_cl, df_pop_cl1, df_pop_cl50, df_aid_embeddings, df_session_embeddings, df_labels,
+                           file_out: str | None, n_items: int | None = None, memory_budget: int = 2 << 30):
+    """retrieve_and_gen_feats of model/retrieve.py:422-657, pandas in / out: candidates with every ranker feature
+    column, written to file_out (parquet, the reference's column names and dtypes, rows sorted by (session,
+    ts_order_aid, aid_next)) and returned. aid_pairs_co_events {rule: R1 frame with all seven columns}; kNN frames
+    [aid, aid_next, dist_w2vec_*, rank_w2vec_*]; df_session_cl [session, cl50]; df_pop_cl1 [aid, rank_*_cl1];
+    df_pop_cl50 [aid, cl50, six rank_*_cl50]; df_aid_embeddings [aid, dim_*]; df_session_embeddings [session,
+    dim_*]; df_labels [session, aid, type] or None (no target columns). Sessions are processed in ranges whose
+    feature columns fit memory_budget bytes on the device."""
+    import pandas as pd
+    job = FeatureJob(df_sessions_aids_full, aid_pairs_co_events, df_knns_w2vec_all, df_knns_w2vec_1_2, df_session_cl,
+                     df_pop_cl1, df_pop_cl50, df_aid_embeddings, df_session_embeddings, df_labels, n_items)
+    table, coff, S = job.table, job.cand_off_host, job.n_sessions
+    max_rows = max(1, int(memory_budget) // sum(dt.itemsize for _, dt in table))
+    writer, frames = None, []
+    if file_out is not None:
+        import pyarrow as pa
+        import pyarrow.parquet as pq
+        os.makedirs(os.path.dirname(os.path.abspath(file_out)), exist_ok=True)
+        schema = pa.schema([(nm, pa.from_numpy_dtype(dt)) for nm, dt in table])
+        writer = pq.ParquetWriter(file_out, schema)
+    lo = 0
+    while True:
+        hi = int(np.searchsorted(coff, coff[lo] + max_rows, side="right")) - 1
+        hi = min(max(hi, lo + 1), S)  # at least one session per range
+        f = job.range(lo, hi)
+        host = {nm: f[nm].cpu().numpy() for nm, _ in table}
+        frames.append(pd.DataFrame(host))
+        if writer is not None:
+            writer.write_table(pa.table({nm: pa.array(host[nm]) for nm, _ in table}, schema=schema))
+        lo = hi
+        if lo >= S:
+            break
+    if writer is not None:
+        writer.close()
+    job.free()
+    return pd.concat(frames, ignore_index=True) if len(frames) > 1 else frames[0]
 
 
 def session_cluster_index(df_session_cl, clusters, sess_ids) -> np.ndarray:
