@@ -272,6 +272,39 @@ static int setup_rules(const ottohip_rule* rules, int n_rules, const ottohip_cov
   return 0;
 }
 
+// k_prep_count2's rule schedule: the first PP_WIN distinct windows around dt = 0 take segment bounds, every other
+// rule searches its session
+static PrepPlan prep_plan(const RulesDev& R) {
+  PrepPlan P;
+  memset(&P, 0, sizeof P);
+  P.sym = R.sym_mask;
+  for (int t = 0; t < 3; ++t)
+    for (int q = 0; q < R.n_of_type[t]; ++q) {
+      const int r = R.rule_of_type[t][q];
+      P.n_rules = std::max(P.n_rules, r + 1);
+      P.types |= (uint32_t)t << (2 * r);
+      P.masks |= (R.mask[r] & 7u) << (3 * r);
+      const bool around = R.lo[r] <= 0 && R.hi[r] >= 0;
+      if (around && ((R.mask[r] >> t) & 1u)) P.ident |= 1u << r;
+    }
+  for (int r = 0; r < P.n_rules; ++r) {  // windows in rule order
+    int w = PP_WIN;
+    if (R.lo[r] <= 0 && R.hi[r] >= 0) {
+      for (w = 0; w < P.nwin; ++w)
+        if (P.wlo[w] == R.lo[r] && P.whi[w] == R.hi[r]) break;
+      if (w == P.nwin && P.nwin < PP_WIN) {
+        P.wlo[w] = R.lo[r]; P.whi[w] = R.hi[r];
+        P.wgap[w] = (uint32_t)std::max(-(int64_t)R.lo[r], (int64_t)R.hi[r]);
+        ++P.nwin;
+      }
+      if (w >= P.nwin) w = PP_WIN;
+    }
+    if (w == PP_WIN) P.any_search = 1;
+    P.wins |= (uint32_t)w << (2 * r);
+  }
+  return P;
+}
+
 static ottohip_table* new_table(ottohip_ctx* ctx, int n_rules, int32_t n_items) {
   ottohip_table* T = new ottohip_table();
   T->device = ctx->device;
@@ -443,8 +476,15 @@ static int covis_front(ottohip_ctx* ctx, const ottohip_events* ev, const ottohip
   if (group) OH_TRY(ws.get("link", (size_t)E, &F.link));
   int ph = ctx->begin("prep_count", s, 9.0 * E + 8.0 * (Sn + 1) + 8.0 * E + 12.0 * E);
   k_block_first<<<grid_for(Sn + 1), 256, 0, s>>>(off, Sn, NB, F.first, F.long_list, n_long);
-  k_prep_count<<<(unsigned)NB, 64, 0, s>>>(off, F.first, NB, ev->aid, ev->ts, ev->type, F.evp, params->n_items,
-                                           params->dedup, err, R, Lt.A, F.cnt, rk, pos_w, fused ? cshift : 0, F.link);
+  // OTTOHIP_PREP=v1 (read per call, A/B switch) keeps the first body of the fused S1+S2 kernel
+  const char* prep_env = getenv("OTTOHIP_PREP");
+  if (prep_env && !strcmp(prep_env, "v1"))
+    k_prep_count<<<(unsigned)NB, 64, 0, s>>>(off, F.first, NB, ev->aid, ev->ts, ev->type, F.evp, params->n_items,
+                                             params->dedup, err, R, Lt.A, F.cnt, rk, pos_w, fused ? cshift : 0, F.link);
+  else
+    k_prep_count2<<<(unsigned)NB, 64, 0, s>>>(off, F.first, NB, ev->aid, ev->ts, ev->type, F.evp, params->n_items,
+                                              params->dedup, err, R, prep_plan(R), Lt.A, F.cnt, rk, pos_w,
+                                              fused ? cshift : 0, F.link);
   if (hipGetLastError() != hipSuccess) { set_error("k_prep_count launch failed"); return OTTOHIP_EHIP; }
   int32_t nl = 0;
   OH_TRY(d2h(&nl, n_long, 1, s));

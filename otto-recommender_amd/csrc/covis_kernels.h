@@ -428,6 +428,10 @@ struct PrepLds {
   uint8_t uns[64];        // session has a ts decrease: full ranking
 };
 static_assert((uint64_t)PB_CAP * MAX_RULES * (LCAP - 1) < (1ull << LK_DSHIFT), "group prefixes in link bits");
+template <class LDS>
+__device__ __forceinline__ void prep_group_rows(LDS& S, const uint32_t (&cv)[PB_CAP / 64], int l, int nch, int nb_ev,
+                                                int64_t E0, int A, uint32_t INV, int cshift, uint32_t* __restrict__ rk,
+                                                uint32_t* __restrict__ link);
 
 __global__ __launch_bounds__(64) void k_prep_count(const int64_t* __restrict__ off, const int64_t* __restrict__ first,
                                                    int64_t NB, const int32_t* __restrict__ aid,
@@ -578,12 +582,15 @@ __global__ __launch_bounds__(64) void k_prep_count(const int64_t* __restrict__ o
         const int t = ev_type(e);
         const int64_t tsi = ev_ts(e);
         int run = -1;
+        int32_t plo = 1, phi = -1;  // the previous rule's window: rules of one type sharing a window share its searches
+        int jb = 0, je = 0;
+#if defined(OH_PREP_ABL) && OH_PREP_ABL == 4  // timing ablation: no identity-run scan (right counts with dedup on)
+        run = 1;
+#endif
 #if defined(OH_PREP_ABL) && OH_PREP_ABL == 3  // timing ablation: no window counts at all, wrong counts
         cn = 1;
         if (false)
 #endif
-        int32_t plo = 1, phi = -1;  // the previous rule's window: rules of one type sharing a window share its searches
-        int jb = 0, je = 0;
         for (int q = 0; q < sR.n_of_type[t]; ++q) {
           const int r = sR.rule_of_type[t][q];
           // a window around dt = 0 ends at or after the event and starts at or before it (the session is in ts
@@ -632,82 +639,462 @@ __global__ __launch_bounds__(64) void k_prep_count(const int64_t* __restrict__ o
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    if (link) {
-      // ---- grouped row entries (LK_REP): events of one session with equal (type, aid) and pairs, found by an LDS
-      // hash over (aid, session, type); each member takes its prefix in the group by one LDS atomic add, the
-      // member that gets 0 is the rep and publishes its position. The hash overlays the dead prefix counts (keys)
-      // and the batch's events (sums: the group keys are read into registers first; the events are stored).
-      uint32_t gk[NCH], sg[NCH];  // sg: the pair count, then slot << 22 | prefix
+    if (link) prep_group_rows(S, cv, l, nch, nb_ev, E0, A, INV, cshift, rk, link);
+    b += nsess;
+  }
+}
+
+// ---- grouped row entries (LK_REP) of one batch (S: PrepLds or PrepLds2; cv: the lane's pair counts per chunk): events
+// of one session with equal (type, aid) and pairs, found by an LDS hash over (aid, session, type); each member takes
+// its prefix in the group by one LDS atomic add, the member that gets 0 is the rep and publishes its position. The
+// hash overlays the dead prefix counts (keys) and the batch's events (sums: the group keys are read into registers
+// first; the events are stored).
+template <class LDS>
+__device__ __forceinline__ void prep_group_rows(LDS& S, const uint32_t (&cv)[PB_CAP / 64], int l, int nch, int nb_ev,
+                                                int64_t E0, int A, uint32_t INV, int cshift, uint32_t* __restrict__ rk,
+                                                uint32_t* __restrict__ link) {
+  constexpr int NCH = PB_CAP / 64;
+  uint32_t gk[NCH], sg[NCH];  // sg: the pair count, then slot << 22 | prefix
 #pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int idx = c * 64 + l;
-        gk[c] = 0u;
-        sg[c] = 0u;
-        if (c < nch && idx < nb_ev) {
-          const uint64_t e = S.key[idx];
-          sg[c] = cv[c];
-          if (e != EV_INVALID && sg[c] != 0)  // aid < 2^23 (the fused layout's bound): the key fits 31 bits
-            gk[c] = (((uint32_t)ev_aid(e) << 8) | ((uint32_t)S.esid[idx] << 2) | (uint32_t)ev_type(e)) + 1u;
-        }
-      }
-      int tb = 6;
-      while ((1 << tb) < 2 * nb_ev && tb < 10) ++tb;
-      const uint32_t TS = 1u << tb;
-      uint32_t* hkey = reinterpret_cast<uint32_t*>(&S.srt[0]);
-      uint32_t* hval = reinterpret_cast<uint32_t*>(&S.key[0]);
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      for (uint32_t i = l; i < TS; i += 64) { hkey[i] = 0u; hval[i] = 0u; }
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      // the first probes of all chunks go out back to back (a wave's LDS operations complete in order, so a later
-      // chunk's probe sees an earlier chunk's insert); the few collisions then walk on, lane by lane. The event whose
-      // probe inserted the key is the group's rep: it sets the group's sum to its own count (prefix 0) and replaces the
-      // key by its position (the probing is over); the other members add their counts, the returned sum is their prefix
-      uint32_t hs[NCH], pv[NCH];
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        hs[c] = (gk[c] * 0x9E3779B1u) >> (32 - tb);
-        pv[c] = gk[c] ? atomicCAS(&hkey[hs[c]], 0u, gk[c]) : 1u;
-      }
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-        while (pv[c] != 0u && pv[c] != gk[c] && gk[c]) {
-          hs[c] = (hs[c] + 1u) & (TS - 1u);
-          pv[c] = atomicCAS(&hkey[hs[c]], 0u, gk[c]);
-        }
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-        if (gk[c] && pv[c] == 0u) { hval[hs[c]] = sg[c]; hkey[hs[c]] = (uint32_t)(c * 64 + l); }
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-        if (gk[c] && pv[c] != 0u) sg[c] = atomicAdd(&hval[hs[c]], sg[c]);
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      // row keys and links: a rep's key carries the group's total (LK_REP | total), a member's link its rep and prefix
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int idx = c * 64 + l;
-        if (c < nch && idx < nb_ev) {
-          uint32_t key = INV, lk = LK_REP, tot = 0u;
-          if (gk[c] && pv[c] == 0u) {
-            tot = hval[hs[c]];
-            const uint32_t g = gk[c] - 1u;
-            key = ((g & 3u) << A) | (g >> 8);
-            lk = LK_REP | tot;
-          } else if (gk[c]) {
-            const int delta = (int)hkey[hs[c]] - idx;
-            lk = ((uint32_t)(delta + 512) << LK_DSHIFT) | sg[c];
-          }
-          rk[E0 + idx] = rk_with_count(key, tot, cshift);
-          link[E0 + idx] = lk;
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  for (int c = 0; c < NCH; ++c) {
+    const int idx = c * 64 + l;
+    gk[c] = 0u;
+    sg[c] = 0u;
+    if (c < nch && idx < nb_ev) {
+      const uint64_t e = S.key[idx];
+      sg[c] = cv[c];
+      if (e != EV_INVALID && sg[c] != 0)  // aid < 2^23 (the fused layout's bound): the key fits 31 bits
+        gk[c] = (((uint32_t)ev_aid(e) << 8) | ((uint32_t)S.esid[idx] << 2) | (uint32_t)ev_type(e)) + 1u;
     }
+  }
+  int tb = 6;
+  while ((1 << tb) < 2 * nb_ev && tb < 10) ++tb;
+  const uint32_t TS = 1u << tb;
+  uint32_t* hkey = reinterpret_cast<uint32_t*>(&S.srt[0]);
+  uint32_t* hval = reinterpret_cast<uint32_t*>(&S.key[0]);
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  for (uint32_t i = l; i < TS; i += 64) { hkey[i] = 0u; hval[i] = 0u; }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  // the first probes of all chunks go out back to back (a wave's LDS operations complete in order, so a later
+  // chunk's probe sees an earlier chunk's insert); the few collisions then walk on, lane by lane. The event whose
+  // probe inserted the key is the group's rep: it sets the group's sum to its own count (prefix 0) and replaces the
+  // key by its position (the probing is over); the other members add their counts, the returned sum is their prefix
+  uint32_t hs[NCH], pv[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    hs[c] = (gk[c] * 0x9E3779B1u) >> (32 - tb);
+    pv[c] = gk[c] ? atomicCAS(&hkey[hs[c]], 0u, gk[c]) : 1u;
+  }
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+    while (pv[c] != 0u && pv[c] != gk[c] && gk[c]) {
+      hs[c] = (hs[c] + 1u) & (TS - 1u);
+      pv[c] = atomicCAS(&hkey[hs[c]], 0u, gk[c]);
+    }
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+    if (gk[c] && pv[c] == 0u) { hval[hs[c]] = sg[c]; hkey[hs[c]] = (uint32_t)(c * 64 + l); }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+    if (gk[c] && pv[c] != 0u) sg[c] = atomicAdd(&hval[hs[c]], sg[c]);
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  // row keys and links: a rep's key carries the group's total (LK_REP | total), a member's link its rep and prefix
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int idx = c * 64 + l;
+    if (c < nch && idx < nb_ev) {
+      uint32_t key = INV, lk = LK_REP, tot = 0u;
+      if (gk[c] && pv[c] == 0u) {
+        tot = hval[hs[c]];
+        const uint32_t g = gk[c] - 1u;
+        key = ((g & 3u) << A) | (g >> 8);
+        lk = LK_REP | tot;
+      } else if (gk[c]) {
+        const int delta = (int)hkey[hs[c]] - idx;
+        lk = ((uint32_t)(delta + 512) << LK_DSHIFT) | sg[c];
+      }
+      rk[E0 + idx] = rk_with_count(key, tot, cshift);
+      link[E0 + idx] = lk;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+}
+
+// ---- S1+S2 fused, second body (the default; OTTOHIP_PREP=v1 keeps k_prep_count). Same batches, same LDS layout of
+// the events, same outputs byte for byte; what differs is how the per-event bookkeeping is found:
+//   session of an event   the session lanes flag their first events; per chunk one ballot of the flags and the last
+//                         flag at or below the lane (carried over chunks) give the session, with no search
+//   ordered check         in the load pass, against the previous lane's ts
+//   sort                  the load pass also notes the chunks where some ts does not rise inside a session; the others
+//                         are sorted as they come (srt = key, written at the load) and skip the sort
+//   deduplication         one pass: the keep ballot places the events (the session's kept-prefix comes from its
+//                         first lane by a shuffle); a chunk that skipped the sort has no duplicates, and with nothing
+//                         dropped before it its events are in place already
+//   window bounds         per distinct window (lo, hi) around dt = 0 (at most PP_WIN of them): with W = max(-lo, hi)
+//                         a segment starts at a session's first event and wherever ts_k - ts_{k-1} > W (every
+//                         EV_INVALID slot is a break too, so the tail is outside every segment). For event i of
+//                         segment [a, b) nothing outside the segment is in its window, and
+//                           jb = a when ts_i - ts_a <= -lo, else the search over [a, i)
+//                           je = b when ts_{b-1} - ts_i <= hi, else the search over [i + 1, b)
+//                         (differences of the biased u32 ts: exact and non-negative in sorted order). The break
+//                         ballots are taken in the store pass (brk, with the last break before the chunk in ca); the
+//                         count pass runs the chunks downwards and carries the first break after the chunk. A chunk
+//                         in and around which both windows have the same breaks finds its segments once.
+//   rule loop             over the rules with a scalar trip count and parameters in scalar registers (PrepPlan),
+//                         lanes predicated by type; the symmetric rule of the lane's type is scanned once, after the
+//                         loop; with dedup on the identity run is 1
+// Rules with a window that is not around 0, or beyond the PP_WIN distinct ones, search the whole session as before.
+constexpr int PP_WIN = 2;
+struct PrepPlan {
+  int32_t n_rules;
+  int32_t nwin;                      // distinct windows around 0 that take segment bounds
+  int32_t wlo[PP_WIN], whi[PP_WIN];
+  uint32_t wgap[PP_WIN];             // W = max(-lo, hi)
+  uint32_t types;                    // 2 bits per rule: this_type
+  uint32_t wins;                     // 2 bits per rule: window index, PP_WIN = searched over the whole session
+  uint32_t masks;                    // 3 bits per rule: next types
+  uint32_t ident;                    // bit per rule: the event is its own partner (identity row subtracted)
+  uint32_t sym;                      // RulesDev::sym_mask
+  uint32_t any_search;               // some rule has wins == PP_WIN
+};
+static_assert(MAX_RULES * 3 <= 32, "PrepPlan packs 3 bits per rule");
+
+struct PrepLds2 {
+  uint64_t key[PB_CAP];   // packed raw events, then the final (sorted, deduplicated) session layout
+  union {                 // srt is dead once the deduplicated layout is in key: pref reuses it
+    uint64_t srt[PB_CAP];
+    uint16_t pref[3][PB_CAP + 1];
+  };
+  uint8_t esid[PB_CAP];   // first the session-start flags (session id at its first event, 0xFF elsewhere), then
+                          // the session of each event; 8-byte aligned: one 64-bit write per lane clears it
+  uint64_t smask[PB_CAP / 64];          // per chunk: ballot of the session starts
+  uint64_t brk[PP_WIN][PB_CAP / 64];    // per window and chunk: ballot of the segment breaks (final layout)
+  uint16_t ca[PP_WIN][PB_CAP / 64];     // the last break before the chunk
+  uint16_t ss[65];
+  uint16_t pst[64], pen[64];
+  uint8_t uns[64];
+};
+static_assert(sizeof(PrepLds2) <= sizeof(PrepLds) + sizeof(RulesDev), "v2 takes no more LDS than v1 (PrepLds + sR)");
+static_assert(PB_CAP == 512, "esid is cleared by 64 lanes x 8 bytes");
+
+// [jb, je): the events in the window (wlo, whi) of event idx (ts tsi, biased tsb) of the segment [a, z), whose first
+// and last events have the biased ts ta and tz; each side falls back to its search on its own
+__device__ __forceinline__ void seg_bounds(const uint64_t* key, int idx, int64_t tsi, uint32_t tsb, int a, int z,
+                                           uint32_t ta, uint32_t tz, int32_t wlo, int32_t whi, int& jb, int& je) {
+#ifdef OH_PREP_NOSEG  // A/B build: every bound by its search inside the segment
+  jb = lds_lower_ts(key, a, idx, tsi + wlo);
+  je = lds_upper_ts(key, idx + 1, z, tsi + whi);
+#else
+  jb = tsb - ta <= (uint32_t)(-(int64_t)wlo) ? a : lds_lower_ts(key, a, idx, tsi + wlo);
+  je = tz - tsb <= (uint32_t)whi ? z : lds_upper_ts(key, idx + 1, z, tsi + whi);
+#endif
+}
+
+__global__ __launch_bounds__(64) void k_prep_count2(const int64_t* __restrict__ off, const int64_t* __restrict__ first,
+                                                    int64_t NB, const int32_t* __restrict__ aid,
+                                                    const int32_t* __restrict__ ts, const int8_t* __restrict__ ty,
+                                                    uint64_t* __restrict__ ev, int n_items, int dedup, int* err,
+                                                    RulesDev R, PrepPlan PL, int A, uint32_t* __restrict__ cnt,
+                                                    uint32_t* __restrict__ rk, uint32_t* __restrict__ pos, int cshift,
+                                                    uint32_t* __restrict__ link) {
+  __shared__ PrepLds2 S;
+  constexpr int NCH = PB_CAP / 64;
+  const int l = threadIdx.x;
+  const int64_t g = blockIdx.x;
+  if (g >= NB) return;
+  const int64_t s0 = first[g], s1 = first[g + 1];
+  const uint32_t INV = 3u << A;
+  const uint64_t le = ~0ull >> (63 - l);  // lanes at or below this one
+  // the valid range of an event's session (ss, pst, pen): read by the searched rules and by the identity run
+  const bool need_sess = PL.any_search != 0 || !dedup;
+  int64_t b = s0;
+  while (b < s1) {
+    const int64_t base = off[b];
+    const int64_t s = b + l;
+    const bool in_s = s < s1;
+    const int64_t so = in_s ? off[s] : 0, se = in_s ? off[s + 1] : 0;
+    const bool ok = in_s && se - base <= PB_CAP && se - so <= LCAP;
+    const uint64_t bad = __ballot(!ok);
+    const int nsess = bad ? (int)__builtin_ctzll(bad) : 64;
+    if (nsess == 0) { ++b; continue; }  // long session: k_prep_long / k_count_long
+    const int nb_ev = __shfl((int)(se - base), nsess - 1);
+    const int64_t E0 = base;
+    // a chunk's events are loaded one chunk ahead: the first chunk's loads fly over the set-up below
+    int32_t a_n = 0, t_n = 0, y_n = 0;
+    if (l < nb_ev) { a_n = aid[E0 + l]; t_n = ts[E0 + l]; y_n = ty[E0 + l]; }
+    if (l < nsess) { S.ss[l] = (uint16_t)(so - base); S.uns[l] = 0; }
+    if (l == 0) S.ss[nsess] = (uint16_t)nb_ev;
+    reinterpret_cast<uint64_t*>(S.esid)[l] = ~0ull;
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    if (l < nsess && se > so) S.esid[so - base] = (uint8_t)l;  // empty sessions have no events to flag
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const int nch = (nb_ev + 63) >> 6;
+    // ---- load, pack, session of each event, ordered check
+    int sid_c = 0;          // the session open at the chunk's first lane
+    uint32_t ts_c = 0;      // the previous chunk's last (biased) ts
+    uint64_t any_uns = 0;
+    // chunks with a lane whose ts is not above its predecessor's in its session, or not below its successor's: only
+    // these can be out of order or hold duplicates; the others are copied to srt here and skip the sort
+    uint32_t slow = 0;
+#pragma unroll 1
+    for (int c = 0; c < nch; ++c) {
+      const int idx = c * 64 + l;
+      const bool in = idx < nb_ev;
+      uint64_t kv = EV_INVALID;
+      int f = 0xFF;
+#ifdef OH_PREP_NOPF  // A/B build: each chunk loads its own events
+      if (c > 0 && in) { a_n = aid[E0 + idx]; t_n = ts[E0 + idx]; y_n = ty[E0 + idx]; }
+      const int32_t a = a_n, t = t_n, y = y_n;
+#else
+      const int32_t a = a_n, t = t_n, y = y_n;
+      if (idx + 64 < nb_ev) { a_n = aid[E0 + idx + 64]; t_n = ts[E0 + idx + 64]; y_n = ty[E0 + idx + 64]; }
+#endif
+      if (in) {
+        if (a < 0 || a >= n_items || y < 0 || y > 2) atomicOr(err, 1);
+        kv = ev_pack(a < 0 ? 0 : a, t, y & 3);
+        S.key[idx] = kv;
+        S.srt[idx] = kv;
+        f = S.esid[idx];
+      }
+      const uint64_t m = __ballot(f != 0xFF);
+      const uint64_t bel = m & le;
+      const int fs = __shfl(f, (63 - (int)__builtin_clzll(bel | 1ull)) & 63);
+      const int sid = bel ? fs : sid_c;
+      if (in) S.esid[idx] = (uint8_t)sid;
+      const uint32_t tsb = (uint32_t)(kv >> 32);
+      uint32_t pv = __shfl_up(tsb, 1);
+      if (l == 0) pv = ts_c;
+      const bool inner = in && !((m >> l) & 1ull);  // not its session's first event
+      const bool dec = inner && tsb < pv;           // a ts decrease inside a session
+      if (dec) S.uns[sid] = 1;
+      any_uns |= __ballot(dec);
+      const uint64_t nup = __ballot(inner && tsb <= pv);
+      if (nup) slow |= (1u << c) | ((nup & 1ull) && c ? 1u << (c - 1) : 0u);  // lane 0: the chunk before holds the twin
+      if (l == 0) S.smask[c] = m;
+      if (m) sid_c = __shfl(f, 63 - (int)__builtin_clzll(m));
+      ts_c = __shfl(tsb, 63);
+    }
+    if (any_uns) slow = ~0u;  // an unordered session is ranked as a whole, over all of its chunks
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    // ---- sort each session (stable rank by the packed key): the slow chunks; every run of equal ts lies in slow
+    // chunks only, so their lanes write exactly their own slots of srt
+#pragma unroll 1
+    for (int c = 0; c < nch; ++c) {
+      if (!((slow >> c) & 1u)) continue;
+      const int idx = c * 64 + l;
+      if (idx >= nb_ev) continue;
+      const int k = S.esid[idx];
+      const uint64_t v = S.key[idx];
+      int lo = S.ss[k], hi = S.ss[k + 1];
+      const bool un = any_uns != 0 && S.uns[k] != 0;
+      if (!un) {  // ts non-decreasing: only the run of equal ts can be out of order
+        const int32_t t = ev_ts(v);
+        int a = idx, e = idx + 1;
+        while (a > lo && ev_ts(S.key[a - 1]) == t) --a;
+        while (e < hi && ev_ts(S.key[e]) == t) ++e;
+        lo = a; hi = e;
+      }
+      int r = lo;
+      for (int j = lo; j < hi; ++j) {
+        const uint64_t u = S.key[j];
+        r += (u < v) | ((u == v) & (j < idx));
+      }
+      S.srt[r] = v;
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    // ---- deduplicate: kept events first, EV_INVALID tail (positions stay inside the session). One pass: a chunk
+    // clears its own slots and then places its kept events at or below them (LDS operations complete in order)
+    {
+      uint32_t P = 0, pst_c = 0;  // kept events so far; the kept-prefix at the start of the session open at lane 0
+      int sp_c = 0;               // that session's first slot
+#pragma unroll 1
+      for (int c = 0; c < nch; ++c) {
+        const int idx = c * 64 + l;
+        const bool in = idx < nb_ev;
+        const uint64_t sm = S.smask[c];
+        if (!((slow >> c) & 1u) && P == (uint32_t)(c * 64) && !need_sess) {
+          // a chunk without equal ts keeps all of its events, and with nothing dropped before it they are in place
+          // (key == srt there since the load); pst / pen are read by the searched rules only
+          P += (uint32_t)(nb_ev - c * 64 < 64 ? nb_ev - c * 64 : 64);
+          if (sm) pst_c = (uint32_t)(sp_c = c * 64 + 63 - (int)__builtin_clzll(sm));
+          continue;
+        }
+        const bool start = (sm >> l) & 1ull;  // flags exist only below nb_ev
+        const uint64_t vv = in ? S.srt[idx] : EV_INVALID;
+        const bool keep = in && (!dedup || start || S.srt[idx - 1] != vv);
+        const uint64_t m = __ballot(keep);
+        const uint32_t Pi = P + mbcnt(m);
+        const uint64_t bel = sm & le;
+        const int src = 63 - (int)__builtin_clzll(bel | 1ull);
+        const uint32_t ps = __shfl(Pi, src & 63);
+        const uint32_t pstl = bel ? ps : pst_c;
+        const int spl = bel ? c * 64 + src : sp_c;
+        if (need_sess) {  // the session ends where the next one starts, or with the batch
+          const uint64_t nx = c + 1 < nch ? S.smask[c + 1] : 1ull;
+          const bool last = in && (idx + 1 == nb_ev || (l < 63 ? (sm >> (l + 1)) & 1ull : nx & 1ull));
+          if (start || last) {
+            const int k = S.esid[idx];
+            if (start) S.pst[k] = (uint16_t)Pi;
+            if (last) S.pen[k] = (uint16_t)(Pi + (keep ? 1u : 0u));
+          }
+        }
+        if (in) S.key[idx] = EV_INVALID;
+        if (keep) S.key[spl + (int)(Pi - pstl)] = vv;
+        P += (uint32_t)__popcll(m);
+        if (sm) {
+          const int h = 63 - (int)__builtin_clzll(sm);
+          pst_c = __shfl(Pi, h);
+          sp_c = c * 64 + h;
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    // ---- store; per-type prefix counts over the batch; segment breaks per window
+    {
+      uint32_t b0 = 0, b1 = 0, b2 = 0;
+      uint32_t tp_c = 0;          // the previous chunk's last (biased) ts
+      int ca0 = 0, ca1 = 0;       // the last break so far, per window
+#pragma unroll 1
+      for (int c = 0; c < nch; ++c) {
+        const int idx = c * 64 + l;
+        const bool in = idx < nb_ev;
+        const uint64_t v = in ? S.key[idx] : EV_INVALID;
+        if (in) ev[E0 + idx] = v;
+        const int t = ev_type(v);
+        const uint64_t m0 = __ballot(t == 0), m1 = __ballot(t == 1), m2 = __ballot(t == 2);
+        if (in) {
+          S.pref[0][idx] = (uint16_t)(b0 + mbcnt(m0));
+          S.pref[1][idx] = (uint16_t)(b1 + mbcnt(m1));
+          S.pref[2][idx] = (uint16_t)(b2 + mbcnt(m2));
+        }
+        b0 += (uint32_t)__popcll(m0); b1 += (uint32_t)__popcll(m1); b2 += (uint32_t)__popcll(m2);
+        const uint32_t tsb = (uint32_t)(v >> 32);
+        uint32_t pv = __shfl_up(tsb, 1);
+        if (l == 0) pv = tp_c;
+        tp_c = __shfl(tsb, 63);
+        // a valid event that is not its session's first follows a valid event of its session: the gap is exact
+        const uint32_t gap = tsb - pv;
+        const bool fix = v == EV_INVALID || ((S.smask[c] >> l) & 1ull);
+        if (PL.nwin > 0) {
+          const uint64_t mb = __ballot(fix || gap > PL.wgap[0]);
+          if (l == 0) { S.brk[0][c] = mb; S.ca[0][c] = (uint16_t)ca0; }
+          if (mb) ca0 = c * 64 + 63 - (int)__builtin_clzll(mb);
+        }
+        if (PL.nwin > 1) {
+          const uint64_t mb = __ballot(fix || gap > PL.wgap[1]);
+          if (l == 0) { S.brk[1][c] = mb; S.ca[1][c] = (uint16_t)ca1; }
+          if (mb) ca1 = c * 64 + 63 - (int)__builtin_clzll(mb);
+        }
+      }
+      if (l == 0) { S.pref[0][nb_ev] = (uint16_t)b0; S.pref[1][nb_ev] = (uint16_t)b1; S.pref[2][nb_ev] = (uint16_t)b2; }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    // ---- partner counts and row keys (chunks downwards: cb = the first break after the chunk)
+    uint32_t cv[NCH];  // grouped rows: the counts of the lane's events (c is wave-uniform: a select per chunk)
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) cv[c] = 0u;
+    int cb0 = nb_ev, cb1 = nb_ev;
+#pragma unroll 1
+    for (int c = nch - 1; c >= 0; --c) {
+      const int idx = c * 64 + l;
+      const bool in = idx < nb_ev;
+      const uint64_t e = in ? S.key[idx] : EV_INVALID;
+      const uint64_t mb0 = PL.nwin > 0 ? S.brk[0][c] : 0ull, mb1 = PL.nwin > 1 ? S.brk[1][c] : 0ull;
+      const int cav0 = PL.nwin > 0 ? (int)S.ca[0][c] : 0, cav1 = PL.nwin > 1 ? (int)S.ca[1][c] : 0;
+      uint32_t cn = 0, key = INV;
+      if (e != EV_INVALID) {
+        const int t = ev_type(e);
+        const int64_t tsi = ev_ts(e);
+        const uint32_t tsb = (uint32_t)(e >> 32);
+        int lo = 0, hi = 0;  // valid events of the session (the searched rules, the identity run without dedup)
+        if (need_sess) {
+          const int k = S.esid[idx];
+          lo = S.ss[k]; hi = lo + (S.pen[k] - S.pst[k]);
+        }
+        int jb0 = 0, je0 = 0, jb1 = 0, je1 = 0;
+        if (PL.nwin > 0) {
+          const uint64_t bel = mb0 & le, abv = mb0 & ~le;
+          const int a0 = bel ? c * 64 + 63 - (int)__builtin_clzll(bel) : cav0;
+          const int z0 = abv ? c * 64 + (int)__builtin_ctzll(abv) : cb0;
+          const uint32_t ta0 = (uint32_t)(S.key[a0] >> 32), tz0 = (uint32_t)(S.key[z0 - 1] >> 32);
+          seg_bounds(S.key, idx, tsi, tsb, a0, z0, ta0, tz0, PL.wlo[0], PL.whi[0], jb0, je0);
+          if (PL.nwin > 1) {
+            int a1 = a0, z1 = z0;
+            uint32_t ta1 = ta0, tz1 = tz0;
+            if (mb1 != mb0 || cav1 != cav0 || cb1 != cb0) {  // the windows' breaks differ in or around this chunk
+              const uint64_t bel1 = mb1 & le, abv1 = mb1 & ~le;
+              a1 = bel1 ? c * 64 + 63 - (int)__builtin_clzll(bel1) : cav1;
+              z1 = abv1 ? c * 64 + (int)__builtin_ctzll(abv1) : cb1;
+              ta1 = (uint32_t)(S.key[a1] >> 32); tz1 = (uint32_t)(S.key[z1 - 1] >> 32);
+            }
+            seg_bounds(S.key, idx, tsi, tsb, a1, z1, ta1, tz1, PL.wlo[1], PL.whi[1], jb1, je1);
+          }
+        }
+        uint32_t run = 1;  // the identity row of :23-27 (and exact twins when dedup is off)
+        if (!dedup) {
+          int a = idx, z = idx + 1;
+          while (a > lo && S.key[a - 1] == e) --a;
+          while (z < hi && S.key[z] == e) ++z;
+          run = (uint32_t)(z - a);
+        }
+        int sjb = 0, sje = 0;  // the window of the symmetric rule of the lane's type (at most one per type)
+        for (int r = 0; r < PL.n_rules; ++r) {
+          if ((int)((PL.types >> (2 * r)) & 3u) != t) continue;
+          const uint32_t w = (PL.wins >> (2 * r)) & 3u;
+          int jb, je;
+          if (w == 0) { jb = jb0; je = je0; }
+          else if (w == 1) { jb = jb1; je = je1; }
+          else {
+            const int32_t rlo = R.lo[r], rhi = R.hi[r];
+            const bool around = rlo <= 0 && rhi >= 0;
+            jb = lds_lower_ts(S.key, lo, around ? idx : hi, tsi + rlo);
+            je = lds_upper_ts(S.key, around ? idx + 1 : jb, hi, tsi + rhi);
+          }
+          if (je <= jb) continue;
+          uint32_t m = 0;
+          if ((PL.sym >> r) & 1u) {
+            sjb = jb; sje = je;
+          } else {
+            const uint32_t mk = (PL.masks >> (3 * r)) & 7u;
+#pragma unroll
+            for (int tt = 0; tt < 3; ++tt)
+              if ((mk >> tt) & 1u) m += (uint32_t)S.pref[tt][je] - (uint32_t)S.pref[tt][jb];
+          }
+          if ((PL.ident >> r) & 1u) m -= run;  // mod 2^32: the symmetric rule's scan is added below
+          cn += m;
+        }
+        if (sje > sjb) cn += count_sym_partners(S.key, sjb, sje, (uint32_t)ev_aid(e), t, A);
+        if (cn) key = ((uint32_t)t << A) | (uint32_t)ev_aid(e);
+      }
+      if (mb0) cb0 = c * 64 + (int)__builtin_ctzll(mb0);
+      if (mb1) cb1 = c * 64 + (int)__builtin_ctzll(mb1);
+      if (in) {
+        cnt[E0 + idx] = cn;
+        if (link) {
+#pragma unroll
+          for (int j = 0; j < NCH; ++j)
+            if (j == c) cv[j] = cn;
+        } else {
+          rk[E0 + idx] = rk_with_count(key, cn, cshift);
+          if (pos) pos[E0 + idx] = (uint32_t)(E0 + idx);
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    if (link) prep_group_rows(S, cv, l, nch, nb_ev, E0, A, INV, cshift, rk, link);
     b += nsess;
   }
 }
