@@ -172,6 +172,8 @@ struct Front {
   uint64_t* evp = nullptr;
   uint64_t* lscr = nullptr;
   uint32_t* lpscr = nullptr;
+  int* err = nullptr;          // S1's range flag, read back with the rows' totals
+  uint32_t *rk = nullptr, *pos = nullptr, *rk2 = nullptr, *pos2 = nullptr;  // S2's row keys, S3's sort buffers
   uint32_t* cnt = nullptr;
   uint32_t* link = nullptr;    // grouped row entries (one-GPU / owner-local fused layout), else null
   uint64_t* poff = nullptr;
@@ -342,21 +344,86 @@ static int owner_map(ottohip_ctx* ctx, int32_t n_items, int G, hipStream_t s, co
   return 0;
 }
 
+static bool env_is(const char* name, const char* value) {
+  const char* v = getenv(name);
+  return v && !strcmp(v, value);
+}
+
+// S3's layout of one count call: every condition and every environment switch of the stage, read once per call.
+// The fused layout (one GPU or owner-local keys, rows < 2^24): S2 writes the row keys with their pair counts in the
+// byte above the sorted key bits (cshift), the sort's first pass generates the event positions itself and drops the
+// keys without a row entry, and one u64 scan carries word offset and row index. Otherwise the unfused layout
+// (k_gather_counts, two scans, k_rows) with 64-bit offsets.
+struct RowsPlan {
+  bool fused = false;
+  bool owner_local = false;  // n_parts > 1: (owner, type, the aid's index among its owner's aids) below the count byte
+  bool group = false;        // one sort entry per (session, type, aid) with pairs; OTTOHIP_GROUP=0: one per event
+  bool try_bucket = false;   // rows_bucket: one GPU, keys of at most 23 bits, u32 offsets; OTTOHIP_ROWS=sort: the sort
+  bool wide = false;         // OTTOHIP_POFF32=0: u64 word offsets although the words are fewer than 2^32
+  bool prep_v1 = false;      // OTTOHIP_PREP=v1: the first body of the fused S1+S2 kernel
+  bool bucket_direct = false, bucket_part = false;  // OTTOHIP_ROWS_DIRECT=1 / OTTOHIP_ROWS_PART=1 (rows_bucket)
+  int cshift = 0;            // first byte above the sorted key bits
+  int kbits = 0;             // sorted key bits; INV: the key of an event without a row; kmask: the key below the count
+  uint32_t kmask = 0, INV = 0;
+  const uint32_t *om_a2l = nullptr, *om_l2a = nullptr, *om_obase = nullptr;  // owner_map (owner_local)
+  int om_lb = 0;
+};
+
+static int rows_plan(ottohip_ctx* ctx, const Layout& Lt, int32_t n_items, int n_parts, hipStream_t s, RowsPlan& P) {
+  P = RowsPlan();
+  P.cshift = (Lt.A + 2 + 7) / 8 * 8;
+  P.INV = 3u << Lt.A;
+  P.kbits = Lt.A + 2;
+  P.kmask = Lt.A + 2 >= 32 ? ~0u : (1u << (Lt.A + 2)) - 1u;
+  const bool fits = P.cshift + 8 <= 32 && 3ull * (uint64_t)n_items < (1ull << 24);
+  // n_parts > 1: the fused layout with owner-local aid indices when (owner, type, local index) and the invalid
+  // key G << (LB + 2) fit below the count byte (OTTOHIP_OWNER_LOCAL=0: the 4-pass owner-key sort)
+  if (fits && n_parts > 1 && !env_is("OTTOHIP_OWNER_LOCAL", "0")) {
+    OH_TRY(owner_map(ctx, n_items, n_parts, s, &P.om_a2l, &P.om_l2a, &P.om_obase, &P.om_lb));
+    P.owner_local = ((uint64_t)n_parts << (P.om_lb + 2)) < (1ull << P.cshift);
+  }
+  P.fused = fits && (n_parts == 1 || P.owner_local);
+  P.group = P.fused && !env_is("OTTOHIP_GROUP", "0");
+  P.wide = env_is("OTTOHIP_POFF32", "0");
+  P.try_bucket = P.fused && n_parts == 1 && P.kbits <= 23 && !env_is("OTTOHIP_ROWS", "sort") && !P.wide;
+  P.prep_v1 = env_is("OTTOHIP_PREP", "v1");
+  P.bucket_direct = env_is("OTTOHIP_ROWS_DIRECT", "1");
+  P.bucket_part = env_is("OTTOHIP_ROWS_PART", "1");
+  return 0;
+}
+
+// S1's range flag, read once the rows' totals are on the host
+static int rows_range_check(const Front& F, hipStream_t s) {
+  int herr = 0;
+  OH_TRY(d2h(&herr, F.err, 1, s));
+  if (herr) { set_error("input out of range: aid outside [0, n_items) or type outside {0,1,2}"); return OTTOHIP_ERANGE; }
+  return 0;
+}
+
+// the rows' outputs for F.Rn rows: row_key, row_begin and one word offset per event, u32 (poff32) or u64 (poff)
+static int rows_alloc(Workspace& ws, Front& F, bool wide) {
+  OH_TRY(ws.get("row_key", (size_t)std::max<int64_t>(F.Rn, 1), &F.row_key));
+  OH_TRY(ws.get("row_begin", (size_t)std::max<int64_t>(F.Rn, 1), &F.row_begin));
+  F.poff = nullptr; F.poff32 = nullptr;
+  if (wide) OH_TRY(ws.get("poff", (size_t)F.E, &F.poff));
+  else OH_TRY(ws.get("poff32", (size_t)F.E, &F.poff32));
+  return 0;
+}
+
 // S3 of the fused layout without the sort's later passes (covis_kernels.h, "bucketed LDS counting sort"): (rks, poss)
 // = radix_skip_pass' output, En entries bucketed by the key's low byte from dstart / ntl on; (rkA, posA) = the idle
-// pair. Sets F.P, F.Rn, F.row_key, F.row_begin and F.poff32 (the reps' offsets: k_link_fix is the caller's) and
-// *taken; *taken stays false, with nothing of F written, when the rows hold 2^32 words or more (the per-key u32
-// totals may have wrapped, and the offsets need 64 bits): the caller finishes the sort instead.
+// pair. Sets F.P, F.Rn, F.row_key, F.row_begin and F.poff32, and *taken; *taken stays false, with nothing of F
+// written, when the rows hold 2^32 words or more (the per-key u32 totals may have wrapped, and the offsets need 64
+// bits): the caller finishes the sort instead.
 // The offsets leave the rank pass in entry order and k_poff_scatter_lds writes them in event order. The two outlets it
-// was measured against stay as A/B switches, read per call: OTTOHIP_ROWS_PART=1, the partition pass + k_poff_scatter
-// of the sort path; OTTOHIP_ROWS_DIRECT=1, the rank pass scatters to poff32 itself.
+// was measured against stay as A/B switches: OTTOHIP_ROWS_PART=1, the partition pass + k_poff_scatter of the sort
+// path; OTTOHIP_ROWS_DIRECT=1, the rank pass scatters to poff32 itself.
 constexpr int64_t RB_MIN_ENTRIES = 1024;
-static int rows_bucket(ottohip_ctx* ctx, Front& F, hipStream_t s, uint32_t* rks, uint32_t* poss, uint32_t* rkA,
-                       uint32_t* posA, int64_t E, int64_t En, const uint64_t* dstart, int ntl, uint32_t kmask,
-                       uint32_t INV, int cshift, const int* err, bool* taken) {
+static int rows_bucket(ottohip_ctx* ctx, Front& F, const RowsPlan& P, hipStream_t s, uint32_t* rks, uint32_t* poss,
+                       uint32_t* rkA, uint32_t* posA, int64_t En, const uint64_t* dstart, int ntl, bool* taken) {
   *taken = false;
   Workspace& ws = ctx->ws;
-  const int nhi = (int)ceil_div((int64_t)INV, 256);  // keys < INV
+  const int nhi = (int)ceil_div((int64_t)P.INV, 256);  // keys < INV
   if (nhi > RB_HI) { set_error("rows_bucket: %d key rows > %d", nhi, RB_HI); return OTTOHIP_EINVAL; }
   const int64_t nk = (int64_t)nhi * 256;
   const uint32_t* csrc = F.link ? F.link : F.cnt;
@@ -367,124 +434,92 @@ static int rows_bucket(ottohip_ctx* ctx, Front& F, hipStream_t s, uint32_t* rks,
   OH_TRY(ws.get("rb_x", (size_t)nk, &x));
   OH_TRY(ws.get("rb_xs", (size_t)nk, &xs));
   const unsigned ntile = (unsigned)ceil_div(nhi, RB_TH);
-  k_rows_bucket_count<<<256, RB_T, 0, s>>>(rks, poss, csrc, En, dstart, ntl, kmask, cshift, nhi, btot, sums);
+  k_rows_bucket_count<<<256, RB_T, 0, s>>>(rks, poss, csrc, En, dstart, ntl, P.kmask, P.cshift, nhi, btot, sums);
   k_rows_bucket_keys<<<ntile, 256, 0, s>>>(btot, nhi, x);
   OH_HIP(hipGetLastError());
   OH_TRY(exclusive_scan_u64(ctx, x, xs, nk, sums + 256, s));
   std::vector<uint64_t> h(257);
   OH_TRY(d2h(h.data(), sums, 257, s));
-  int herr = 0;
-  OH_TRY(d2h(&herr, err, 1, s));
-  if (herr) { set_error("input out of range: aid outside [0, n_items) or type outside {0,1,2}"); return OTTOHIP_ERANGE; }
+  OH_TRY(rows_range_check(F, s));
   uint64_t words = 0;
   for (int d = 0; d < 256; ++d) words += h[d];
   if (words >= (1ull << 32)) return 0;
   const uint64_t X = h[256];
   F.P = X >> 24;
   F.Rn = (int64_t)(X & 0xFFFFFFull);
-  OH_TRY(ws.get("row_key", (size_t)std::max<int64_t>(F.Rn, 1), &F.row_key));
-  OH_TRY(ws.get("row_begin", (size_t)std::max<int64_t>(F.Rn, 1), &F.row_begin));
-  F.poff = nullptr;
-  OH_TRY(ws.get("poff32", (size_t)E, &F.poff32));
+  OH_TRY(rows_alloc(ws, F, false));
   uint32_t* wbase = btot;  // the totals are spent
   k_rows_bucket_layout<<<ntile, 256, 0, s>>>(x, xs, nhi, F.row_key, F.row_begin, wbase);
   // dstart stays the first pass' until the partition outlet's radix pass, after the rank pass
-  const char *denv = getenv("OTTOHIP_ROWS_DIRECT"), *penv = getenv("OTTOHIP_ROWS_PART");
-  if (denv && !strcmp(denv, "1")) {
-    k_rows_bucket_rank<true><<<256, RB_T, 0, s>>>(rks, poss, csrc, En, dstart, ntl, kmask, cshift, nhi, wbase, F.poff32,
-                                                  nullptr);
+  if (P.bucket_direct) {
+    k_rows_bucket_rank<true><<<256, RB_T, 0, s>>>(rks, poss, csrc, En, dstart, ntl, P.kmask, P.cshift, nhi, wbase,
+                                                  F.poff32, nullptr);
   } else {
-    k_rows_bucket_rank<false><<<256, RB_T, 0, s>>>(rks, poss, csrc, En, dstart, ntl, kmask, cshift, nhi, wbase, nullptr,
-                                                   rkA);
-    if (penv && !strcmp(penv, "1")) {
-      OH_TRY(radix_pass(ctx, poss, rkA, posA, rks, En, std::max(0, bits_for((uint64_t)E) - 8), s));
+    k_rows_bucket_rank<false><<<256, RB_T, 0, s>>>(rks, poss, csrc, En, dstart, ntl, P.kmask, P.cshift, nhi, wbase,
+                                                   nullptr, rkA);
+    if (P.bucket_part) {
+      OH_TRY(radix_pass(ctx, poss, rkA, posA, rks, En, std::max(0, bits_for((uint64_t)F.E) - 8), s));
       k_poff_scatter<<<grid_for(En), 256, 0, s>>>(posA, rks, En, F.poff32);
     } else {
       constexpr int gt = PL_EV / RADIX_TILE_KEYS;
       static_assert(gt >= 1, "an LDS image holds at least one sort tile of events");
-      k_poff_scatter_lds<<<(unsigned)ceil_div(ntl, gt), PL_T, 0, s>>>(poss, rkA, En, dstart, ntl, gt, RADIX_TILE_KEYS, E,
-                                                                    F.poff32);
+      k_poff_scatter_lds<<<(unsigned)ceil_div(ntl, gt), PL_T, 0, s>>>(poss, rkA, En, dstart, ntl, gt, RADIX_TILE_KEYS,
+                                                                    F.E, F.poff32);
     }
   }
+  // grouped row entries: every member's word offset from its rep's (the emit reads one offset per event)
+  if (F.link) k_link_fix<<<grid_for(F.E, 256 * LF_PER), 256, 0, s>>>(F.link, F.E, F.poff32, F.poff);
   OH_HIP(hipGetLastError());
   *taken = true;
   return 0;
 }
 
-// S1 prep, S2 count, S3 rows. n_parts > 1: owner-major rows, and (emit handle) owner bounds.
-static int covis_front(ottohip_ctx* ctx, const ottohip_events* ev, const ottohip_covis_params* params,
-                       const int32_t* file_ids, int n_parts, Front& F, hipStream_t s, ottohip_emit* EM = nullptr) {
-  ++ctx->gen;
-  const int64_t E = ev->n_events, Sn = ev->n_sessions;
-  F.E = E; F.Sn = Sn;
-  F.P = 0; F.Rn = 0;
-  if (E == 0 || Sn == 0) return 0;
+// S1 prep + S2 count (fused; sessions longer than LCAP: separate per-session kernels): the packed events, the pair
+// counts and the row keys (fused layout: with the count byte, and the link array of the grouped entries)
+static int front_prep_count(ottohip_ctx* ctx, const ottohip_events* ev, const ottohip_covis_params* params,
+                            const int32_t* file_ids, Front& F, const RowsPlan& P, hipStream_t s) {
   Workspace& ws = ctx->ws;
   const Layout& Lt = F.Lt;
   const RulesDev& R = F.R;
+  const int64_t E = F.E, Sn = F.Sn;
   const int64_t NB = ceil_div(E, EV_BLOCK);
   F.NB = NB;
   int32_t* n_long;
-  int* err;
   const int64_t long_cap = E / (LCAP + 1) + 1;
   OH_TRY(ws.get("first", (size_t)NB + 1, &F.first));
   OH_TRY(ws.get("fb", (size_t)ev->n_files + 1, &F.fb));
   OH_TRY(ws.get("fid", (size_t)ev->n_files, &F.fid));
   OH_TRY(ws.get("long_list", (size_t)long_cap, &F.long_list));
   OH_TRY(ws.get("n_long", 4, &n_long));
-  OH_TRY(ws.get("err", 4, &err));
+  OH_TRY(ws.get("err", 4, &F.err));
   std::vector<uint32_t> fid(ev->n_files);
   for (int f = 0; f < ev->n_files; ++f) fid[f] = file_ids ? (uint32_t)file_ids[f] : (uint32_t)f;
   OH_HIP(hipMemcpyAsync(F.fb, ev->file_session_bounds, (ev->n_files + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
   OH_HIP(hipMemcpyAsync(F.fid, fid.data(), ev->n_files * sizeof(uint32_t), hipMemcpyHostToDevice, s));
   OH_HIP(hipMemsetAsync(n_long, 0, 4 * sizeof(int32_t), s));
-  OH_HIP(hipMemsetAsync(err, 0, sizeof(int), s));
+  OH_HIP(hipMemsetAsync(F.err, 0, sizeof(int), s));
   OH_HIP(hipStreamSynchronize(s));  // fid is a stack vector
   const int64_t* off = ev->session_offsets;
   F.off = off;
-
-  // ---- S1 prep + S2 count (fused; sessions longer than LCAP: separate per-session kernels)
-  uint32_t *rk, *pos, *rk2, *pos2;
   OH_TRY(ws.get("ev", (size_t)E, &F.evp));
   OH_TRY(ws.get("cnt", (size_t)E, &F.cnt));
-  OH_TRY(ws.get("rk", (size_t)E, &rk));
-  OH_TRY(ws.get("pos", (size_t)E, &pos));
-  OH_TRY(ws.get("rk2", (size_t)E, &rk2));
-  OH_TRY(ws.get("pos2", (size_t)E, &pos2));
-  // S3's fused row layout (one GPU, rows < 2^24): S2 writes the row keys with their pair counts in
-  // the byte above the sorted key bits, and the sort generates the event positions itself
-  static const bool rows_legacy = getenv("OTTOHIP_ROWS") && !strcmp(getenv("OTTOHIP_ROWS"), "legacy");
-  const int cshift = (Lt.A + 2 + 7) / 8 * 8;  // first byte above the sorted key bits
-  // n_parts > 1: the fused layout with owner-local aid indices when (owner, type, local index) and the invalid
-  // key G << (LB + 2) fit below the count byte (OTTOHIP_OWNER_LOCAL=0: the 4-pass owner-key sort)
-  const bool ol_env = !(getenv("OTTOHIP_OWNER_LOCAL") && !strcmp(getenv("OTTOHIP_OWNER_LOCAL"), "0"));  // per call
-  const uint32_t *om_a2l = nullptr, *om_l2a = nullptr, *om_obase = nullptr;
-  int om_lb = 0;
-  bool owner_local = false;
-  if (!rows_legacy && n_parts > 1 && ol_env && cshift + 8 <= 32 && 3ull * (uint64_t)params->n_items < (1ull << 24)) {
-    OH_TRY(owner_map(ctx, params->n_items, n_parts, s, &om_a2l, &om_l2a, &om_obase, &om_lb));
-    owner_local = ((uint64_t)n_parts << (om_lb + 2)) < (1ull << cshift);
-  }
-  const bool fused = !rows_legacy && (n_parts == 1 || owner_local) && cshift + 8 <= 32 &&
-                     3ull * (uint64_t)params->n_items < (1ull << 24);
-  uint32_t* pos_w = fused ? nullptr : pos;
-  static const bool rows_atomic = getenv("OTTOHIP_ROWS") && !strcmp(getenv("OTTOHIP_ROWS"), "atomic");
-  // grouped row entries (fused layout): one S3 sort entry per (session, type, aid) with pairs; OTTOHIP_GROUP=0: one per
-  // event (read per call, A/B switch)
-  const bool group = fused && !rows_atomic && !(getenv("OTTOHIP_GROUP") && !strcmp(getenv("OTTOHIP_GROUP"), "0"));
+  OH_TRY(ws.get("rk", (size_t)E, &F.rk));
+  OH_TRY(ws.get("pos", (size_t)E, &F.pos));
+  OH_TRY(ws.get("rk2", (size_t)E, &F.rk2));
+  OH_TRY(ws.get("pos2", (size_t)E, &F.pos2));
   F.link = nullptr;
-  if (group) OH_TRY(ws.get("link", (size_t)E, &F.link));
+  if (P.group) OH_TRY(ws.get("link", (size_t)E, &F.link));
+  uint32_t* rk = F.rk;
+  uint32_t* pos_w = P.fused ? nullptr : F.pos;  // fused: the sort generates the event positions
+  const int cs = P.fused ? P.cshift : 0;
   int ph = ctx->begin("prep_count", s, 9.0 * E + 8.0 * (Sn + 1) + 8.0 * E + 12.0 * E);
   k_block_first<<<grid_for(Sn + 1), 256, 0, s>>>(off, Sn, NB, F.first, F.long_list, n_long);
-  // OTTOHIP_PREP=v1 (read per call, A/B switch) keeps the first body of the fused S1+S2 kernel
-  const char* prep_env = getenv("OTTOHIP_PREP");
-  if (prep_env && !strcmp(prep_env, "v1"))
+  if (P.prep_v1)
     k_prep_count<<<(unsigned)NB, 64, 0, s>>>(off, F.first, NB, ev->aid, ev->ts, ev->type, F.evp, params->n_items,
-                                             params->dedup, err, R, Lt.A, F.cnt, rk, pos_w, fused ? cshift : 0, F.link);
+                                             params->dedup, F.err, R, Lt.A, F.cnt, rk, pos_w, cs, F.link);
   else
     k_prep_count2<<<(unsigned)NB, 64, 0, s>>>(off, F.first, NB, ev->aid, ev->ts, ev->type, F.evp, params->n_items,
-                                              params->dedup, err, R, prep_plan(R), Lt.A, F.cnt, rk, pos_w,
-                                              fused ? cshift : 0, F.link);
+                                              params->dedup, F.err, R, prep_plan(R), Lt.A, F.cnt, rk, pos_w, cs, F.link);
   if (hipGetLastError() != hipSuccess) { set_error("k_prep_count launch failed"); return OTTOHIP_EHIP; }
   int32_t nl = 0;
   OH_TRY(d2h(&nl, n_long, 1, s));
@@ -506,176 +541,141 @@ static int covis_front(ottohip_ctx* ctx, const ottohip_events* ev, const ottohip
     OH_TRY(ws.get("long_off", (size_t)(nl + 1), &F.d_loff));
     OH_HIP(hipMemcpy(F.d_loff, loff.data(), (nl + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     k_prep_long<<<nl, 64, 0, s>>>(off, F.long_list, F.d_loff, F.lscr, ev->aid, ev->ts, ev->type, F.evp,
-                                  params->n_items, params->dedup, err);
-    k_count_long<<<nl, 64, 0, s>>>(off, F.long_list, F.d_loff, F.lscr, F.lpscr, F.evp, R, Lt.A, F.cnt, rk, pos_w,
-                                   fused ? cshift : 0, F.link);
+                                  params->n_items, params->dedup, F.err);
+    k_count_long<<<nl, 64, 0, s>>>(off, F.long_list, F.d_loff, F.lscr, F.lpscr, F.evp, R, Lt.A, F.cnt, rk, pos_w, cs,
+                                   F.link);
     if (hipGetLastError() != hipSuccess) { set_error("long-session launch failed"); return OTTOHIP_EHIP; }
   }
   ctx->end(ph, s);
+  return 0;
+}
 
-  // ---- S3 rows (aid-major transpose; owner-major first when n_parts > 1)
-  ph = ctx->begin("rows", s, 0);
-  if (rows_atomic && fused) {  // no sort: dense rows, per-event ranks by returning atomics (k_rows_atomic)
-    const uint32_t INVa = 3u << Lt.A;
-    const uint32_t kmask_a = Lt.A + 2 >= 32 ? ~0u : (1u << (Lt.A + 2)) - 1u;
-    const int64_t nk = (int64_t)3 << Lt.A;  // dense (type, aid) keys
-    uint32_t* dcnt;
-    uint64_t *doff, *tot;
-    OH_TRY(ws.get("ra_cnt", (size_t)(nk * RA_SUB), &dcnt));
-    OH_TRY(ws.get("ra_off", (size_t)(nk * RA_SUB), &doff));
-    OH_TRY(ws.get("tot", 4, &tot));
-    OH_HIP(hipMemsetAsync(dcnt, 0, (size_t)(nk * RA_SUB) * 4, s));
-    k_rows_atomic<<<grid_for(E, 256 * RA_PER), 256, 0, s>>>(rk, F.cnt, E, kmask_a, INVa, dcnt, pos);
-    OH_TRY(exclusive_scan_u32(ctx, dcnt, doff, nk * RA_SUB, tot, s));
-    uint64_t PP = 0;
-    OH_TRY(d2h(&PP, tot, 1, s));
-    int herr = 0;
-    OH_TRY(d2h(&herr, err, 1, s));
-    if (herr) { set_error("input out of range: aid outside [0, n_items) or type outside {0,1,2}"); return OTTOHIP_ERANGE; }
-    F.P = PP;
-    F.Rn = nk;
-    OH_TRY(ws.get("row_key", (size_t)nk, &F.row_key));
-    OH_TRY(ws.get("row_begin", (size_t)nk, &F.row_begin));
-    k_rows_dense<<<grid_for(nk), 256, 0, s>>>(doff, nk, F.row_key, F.row_begin);
-    F.poff = nullptr; F.poff32 = nullptr;
-    if (F.P < (1ull << 32)) OH_TRY(ws.get("poff32", (size_t)E, &F.poff32));
-    else OH_TRY(ws.get("poff", (size_t)E, &F.poff));
-    k_rows_atomic_off<<<grid_for(E, 256 * RA_PER), 256, 0, s>>>(rk, E, kmask_a, INVa, doff, pos, F.poff32, F.poff);
-    OH_HIP(hipGetLastError());
-    ctx->end(ph, s);
-    return 0;
-  }
-  uint32_t INV = 3u << Lt.A;
-  int kbits = Lt.A + 2;
-  uint32_t kmask = Lt.A + 2 >= 32 ? ~0u : (1u << (Lt.A + 2)) - 1u;
-  if (owner_local) {
-    const uint32_t INV2 = (uint32_t)n_parts << (om_lb + 2);
-    k_owner_key_local<<<grid_for(E), 256, 0, s>>>(rk, E, INV, Lt.A, (uint32_t)n_parts, om_lb, INV2,
-                                                 (1u << cshift) - 1u, om_a2l);
-    INV = INV2;
-    kbits = bits_for((uint64_t)INV2 + 1);
-    kmask = (1u << cshift) - 1u;
+// n_parts > 1: the row keys become owner-major, so every owner's rows and words are contiguous; P's key fields follow
+static int rows_owner_keys(const Front& F, RowsPlan& P, int n_parts, hipStream_t s) {
+  const int A = F.Lt.A;
+  if (P.owner_local) {
+    const uint32_t INV2 = (uint32_t)n_parts << (P.om_lb + 2);
+    k_owner_key_local<<<grid_for(F.E), 256, 0, s>>>(F.rk, F.E, P.INV, A, (uint32_t)n_parts, P.om_lb, INV2,
+                                                   (1u << P.cshift) - 1u, P.om_a2l);
+    P.INV = INV2;
+    P.kbits = bits_for((uint64_t)INV2 + 1);
+    P.kmask = (1u << P.cshift) - 1u;
   } else if (n_parts > 1) {
-    const uint32_t INV2 = (uint32_t)n_parts << (Lt.A + 2);
-    k_owner_key<<<grid_for(E), 256, 0, s>>>(rk, E, INV, Lt.A, (uint32_t)n_parts, INV2);
-    INV = INV2;
-    kbits = Lt.A + 2 + bits_for((uint64_t)n_parts + 1);
-    if (kbits > 32) { set_error("row key with owner bits > 32 bits"); return OTTOHIP_ELIMIT; }
+    const uint32_t INV2 = (uint32_t)n_parts << (A + 2);
+    k_owner_key<<<grid_for(F.E), 256, 0, s>>>(F.rk, F.E, P.INV, A, (uint32_t)n_parts, INV2);
+    P.INV = INV2;
+    P.kbits = A + 2 + bits_for((uint64_t)n_parts + 1);
+    if (P.kbits > 32) { set_error("row key with owner bits > 32 bits"); return OTTOHIP_ELIMIT; }
   }
-  // fused layout: counts ride in the keys' spare bits (written by S2), one u64 scan carries word
-  // offset and row index; the sort's first pass takes the event positions from its own indices
-  uint32_t *rks = rk, *poss = pos;
-  // fused layout: the sort's first pass drops the keys without a row entry (events without pairs; grouped: members),
-  // the later passes and the row passes below run over the En kept entries
-  int64_t En = E;
-  const SortSkip skip{fused ? (1u << cshift) - 1u : 0u, INV, &En};
-  // bucketed rows (rows_bucket): one GPU, keys of at most 23 bits, u32 word offsets, more than a few entries;
-  // OTTOHIP_ROWS=sort (read per call, A/B switch) keeps the sort
-  const char* rows_env = getenv("OTTOHIP_ROWS");
-  const char* p32_env = getenv("OTTOHIP_POFF32");
-  bool bucketed = false;
-  if (fused && n_parts == 1 && kbits <= 23 && !(rows_env && !strcmp(rows_env, "sort")) &&
-      !(p32_env && !strcmp(p32_env, "0"))) {
-    const uint64_t* dstart = nullptr;
-    int ntl = 0;
-    OH_TRY(radix_skip_pass(ctx, rk, rk2, pos2, E, s, skip, &dstart, &ntl));
-    rks = rk2; poss = pos2;
-    if (En > RB_MIN_ENTRIES)
-      OH_TRY(rows_bucket(ctx, F, s, rk2, pos2, rk, pos, E, En, dstart, ntl, kmask, INV, cshift, err, &bucketed));
-    // not taken (few entries, or 2^32 words or more): the sort's remaining passes
-    if (!bucketed) OH_TRY(radix_sort_pairs(ctx, rks, poss, rk, pos, En, kbits, s, false, nullptr, 8));
-  } else {
-    OH_TRY(radix_sort_pairs(ctx, rks, poss, rk2, pos2, E, kbits, s, fused, fused ? &skip : nullptr));
-  }
-  uint64_t* tot;
+  OH_HIP(hipGetLastError());
+  return 0;
+}
+
+// S3 of the fused layout after the full sort: (rks, poss) = the En kept entries in key order. k_rows_sums + one u64
+// scan of (count << 24 | row start), then one tile pass gives word offsets, row keys and row starts.
+static int rows_fused_sorted(ottohip_ctx* ctx, Front& F, const RowsPlan& P, hipStream_t s, uint32_t* rks,
+                             uint32_t* poss, int64_t En) {
+  Workspace& ws = ctx->ws;
+  // saturated count bytes are read back from the link array (grouped: the group's total) or the counts
+  const uint32_t* csrc = F.link ? F.link : F.cnt;
+  const int64_t nb = ceil_div(En, RT_TILE);
+  uint64_t *bsum, *boff, *tot;
+  OH_TRY(ws.get("rt_sums", (size_t)std::max<int64_t>(nb, 1), &bsum));
+  OH_TRY(ws.get("rt_offs", (size_t)std::max<int64_t>(nb, 1), &boff));
   OH_TRY(ws.get("tot", 4, &tot));
-  if (bucketed) {
-    if (F.link) k_link_fix<<<grid_for(E, 256 * LF_PER), 256, 0, s>>>(F.link, E, F.poff32, F.poff);
-    OH_HIP(hipGetLastError());
-    ctx->end(ph, s);
-    return 0;
+  if (nb > 0) k_rows_sums<<<(unsigned)nb, RT_T, 0, s>>>(rks, poss, csrc, En, P.kmask, P.INV, P.cshift, bsum);
+  OH_TRY(exclusive_scan_u64(ctx, bsum, boff, nb, tot, s));
+  uint64_t X = 0;
+  OH_TRY(d2h(&X, tot, 1, s));
+  OH_TRY(rows_range_check(F, s));
+  F.P = X >> 24;
+  F.Rn = (int64_t)(X & 0xFFFFFFull);
+  // word offsets below 2^32: u32 per event (the random scatter of one offset per event and the
+  // emit's reads move half the bytes; measured rows 12.3 -> 11.1 ms at 220 M events)
+  OH_TRY(rows_alloc(ws, F, P.wide || F.P >= (1ull << 32)));
+  if (F.poff32 && En > 4096) {
+    // the offsets leave the tile pass in sorted order (coalesced), one radix pass partitions the
+    // (position, offset) pairs by the positions' top 8 bits, and the final scatter writes one
+    // 1/256 slice of poff32 at a time; a few entries are scattered by the tile pass directly
+    uint32_t* rkA = rks == F.rk ? F.rk2 : F.rk;  // the sort's idle pair
+    uint32_t* posA = poss == F.pos ? F.pos2 : F.pos;
+    k_rows_tile<<<(unsigned)nb, RT_T, 0, s>>>(rks, poss, csrc, En, P.kmask, P.INV, P.cshift, boff, nullptr, F.poff32,
+                                              F.row_key, F.row_begin, rkA);
+    OH_TRY(radix_pass(ctx, poss, rkA, posA, rks, En, std::max(0, bits_for((uint64_t)F.E) - 8), s));
+    k_poff_scatter<<<grid_for(En), 256, 0, s>>>(posA, rks, En, F.poff32);
+  } else if (nb > 0) {
+    k_rows_tile<<<(unsigned)nb, RT_T, 0, s>>>(rks, poss, csrc, En, P.kmask, P.INV, P.cshift, boff, F.poff, F.poff32,
+                                              F.row_key, F.row_begin);
   }
-  if (fused) {
-    // saturated count bytes are read back from the link array (grouped: the group's total) or the counts
-    const uint32_t* csrc = F.link ? F.link : F.cnt;
-    const int64_t nb = ceil_div(En, RT_TILE);
-    uint64_t *bsum, *boff;
-    OH_TRY(ws.get("rt_sums", (size_t)std::max<int64_t>(nb, 1), &bsum));
-    OH_TRY(ws.get("rt_offs", (size_t)std::max<int64_t>(nb, 1), &boff));
-    if (nb > 0) k_rows_sums<<<(unsigned)nb, RT_T, 0, s>>>(rks, poss, csrc, En, kmask, INV, cshift, bsum);
-    OH_TRY(exclusive_scan_u64(ctx, bsum, boff, nb, tot, s));
-    uint64_t X = 0;
-    OH_TRY(d2h(&X, tot, 1, s));
-    int herr = 0;
-    OH_TRY(d2h(&herr, err, 1, s));
-    if (herr) { set_error("input out of range: aid outside [0, n_items) or type outside {0,1,2}"); return OTTOHIP_ERANGE; }
-    F.P = X >> 24;
-    F.Rn = (int64_t)(X & 0xFFFFFFull);
-    OH_TRY(ws.get("row_key", (size_t)std::max<int64_t>(F.Rn, 1), &F.row_key));
-    OH_TRY(ws.get("row_begin", (size_t)std::max<int64_t>(F.Rn, 1), &F.row_begin));
-    // word offsets below 2^32: u32 per event (the random scatter of one offset per event and the
-    // emit's reads move half the bytes; measured rows 12.3 -> 11.1 ms at 220 M events)
-    static const char* p32env = getenv("OTTOHIP_POFF32");  // A/B switch: 0 = u64 offsets
-    F.poff = nullptr; F.poff32 = nullptr;
-    if (F.P < (1ull << 32) && !(p32env && !strcmp(p32env, "0"))) {
-      OH_TRY(ws.get("poff32", (size_t)E, &F.poff32));
-      // the offsets leave the tile pass in sorted order (coalesced), one radix pass partitions the
-      // (position, offset) pairs by the positions' top 8 bits, and the final scatter writes one
-      // 1/256 slice of poff32 at a time (OTTOHIP_POFF_PART=0: the tile pass scatters directly)
-      static const char* ppenv = getenv("OTTOHIP_POFF_PART");  // A/B switch
-      if (!(ppenv && !strcmp(ppenv, "0")) && En > 4096) {
-        uint32_t* rkA = rks == rk ? rk2 : rk;  // the sort's idle pair
-        uint32_t* posA = poss == pos ? pos2 : pos;
-        k_rows_tile<<<(unsigned)nb, RT_T, 0, s>>>(rks, poss, csrc, En, kmask, INV, cshift, boff, nullptr, F.poff32, 0u,
-                                                  0xFFFFFFFFu, 1, F.row_key, F.row_begin, rkA);
-        const uint64_t* dstart = nullptr;
-        int ntl = 0;
-        OH_TRY(radix_pass(ctx, poss, rkA, posA, rks, En, std::max(0, bits_for((uint64_t)E) - 8), s, &dstart, &ntl));
-        // OTTOHIP_POFF_XCD=1: the XCD-aware scatter (A/B switch, off: 6.47 vs 6.85 GB written per build, slower)
-        static const bool pxcd = getenv("OTTOHIP_POFF_XCD") && !strcmp(getenv("OTTOHIP_POFF_XCD"), "1");
-        if (pxcd)
-          k_poff_scatter_xcd<<<(unsigned)(8 * std::max(1, ctx->n_cu)), 256, 0, s>>>(posA, rks, En, dstart, ntl, F.poff32);
-        else
-          k_poff_scatter<<<grid_for(En), 256, 0, s>>>(posA, rks, En, F.poff32);
-      } else if (nb > 0) {
-        k_rows_tile<<<(unsigned)nb, RT_T, 0, s>>>(rks, poss, csrc, En, kmask, INV, cshift, boff, nullptr, F.poff32, 0u,
-                                                  0xFFFFFFFFu, 1, F.row_key, F.row_begin);
-      }
-    } else {
-      OH_TRY(ws.get("poff", (size_t)E, &F.poff));
-      if (nb > 0)
-        k_rows_tile<<<(unsigned)nb, RT_T, 0, s>>>(rks, poss, csrc, En, kmask, INV, cshift, boff, F.poff, nullptr, 0u, 0u,
-                                                  1, F.row_key, F.row_begin);
-    }
-    // grouped row entries: every member's word offset from its rep's (the emit reads one offset per event)
-    if (F.link) k_link_fix<<<grid_for(E, 256 * LF_PER), 256, 0, s>>>(F.link, E, F.poff32, F.poff);
-    // owner-local keys back to (type, aid): the rows downstream (owner bounds, pieces, reduce) read those
-    if (owner_local && F.Rn > 0)
-      k_rows_decode<<<grid_for(F.Rn), 256, 0, s>>>(F.row_key, F.Rn, Lt.A, om_lb, om_obase, om_l2a);
-    OH_HIP(hipGetLastError());
-    ctx->end(ph, s);
-    return 0;
-  }
-  uint32_t *c_sorted = (rks == rk) ? rk2 : rk, *row_flag = (poss == pos) ? pos2 : pos;  // reuse the idle pair
-  k_gather_counts<<<grid_for(E), 256, 0, s>>>(rks, poss, F.cnt, E, INV, c_sorted, row_flag);
-  uint64_t *woff, *row_idx;
+  // grouped row entries: every member's word offset from its rep's (the emit reads one offset per event)
+  if (F.link) k_link_fix<<<grid_for(F.E, 256 * LF_PER), 256, 0, s>>>(F.link, F.E, F.poff32, F.poff);
+  // owner-local keys back to (type, aid): the rows downstream (owner bounds, pieces, reduce) read those
+  if (P.owner_local && F.Rn > 0)
+    k_rows_decode<<<grid_for(F.Rn), 256, 0, s>>>(F.row_key, F.Rn, F.Lt.A, P.om_lb, P.om_obase, P.om_l2a);
+  OH_HIP(hipGetLastError());
+  return 0;
+}
+
+// S3 of the unfused layout (keys too wide for the count byte, or the owner-key sort): (rks, poss) = all E events in
+// key order; the counts are gathered into sorted order, one scan each gives word offsets and row indices
+static int rows_unfused(ottohip_ctx* ctx, Front& F, const RowsPlan& P, hipStream_t s, uint32_t* rks, uint32_t* poss) {
+  Workspace& ws = ctx->ws;
+  const int64_t E = F.E;
+  uint32_t *c_sorted = (rks == F.rk) ? F.rk2 : F.rk, *row_flag = (poss == F.pos) ? F.pos2 : F.pos;  // the idle pair
+  k_gather_counts<<<grid_for(E), 256, 0, s>>>(rks, poss, F.cnt, E, P.INV, c_sorted, row_flag);
+  uint64_t *woff, *row_idx, *tot;
   OH_TRY(ws.get("woff", (size_t)E, &woff));
   OH_TRY(ws.get("row_idx", (size_t)E, &row_idx));
+  OH_TRY(ws.get("tot", 4, &tot));
   OH_TRY(exclusive_scan_u32(ctx, c_sorted, woff, E, tot, s));
   OH_TRY(exclusive_scan_u32(ctx, row_flag, row_idx, E, tot + 1, s));
   uint64_t PR[2];
   OH_TRY(d2h(PR, tot, 2, s));
-  int herr = 0;
-  OH_TRY(d2h(&herr, err, 1, s));
-  if (herr) { set_error("input out of range: aid outside [0, n_items) or type outside {0,1,2}"); return OTTOHIP_ERANGE; }
+  OH_TRY(rows_range_check(F, s));
   F.P = PR[0];
   F.Rn = (int64_t)PR[1];
-  OH_TRY(ws.get("poff", (size_t)E, &F.poff));
-  F.poff32 = nullptr;
-  OH_TRY(ws.get("row_key", (size_t)std::max<int64_t>(F.Rn, 1), &F.row_key));
-  OH_TRY(ws.get("row_begin", (size_t)std::max<int64_t>(F.Rn, 1), &F.row_begin));
-  k_rows<<<grid_for(E), 256, 0, s>>>(rks, poss, E, INV, kmask, woff, row_flag, row_idx, F.poff, F.row_key,
+  OH_TRY(rows_alloc(ws, F, true));
+  k_rows<<<grid_for(E), 256, 0, s>>>(rks, poss, E, P.INV, P.kmask, woff, row_flag, row_idx, F.poff, F.row_key,
                                      F.row_begin);
+  OH_HIP(hipGetLastError());
+  return 0;
+}
+
+// S1 prep, S2 count, S3 rows (aid-major transpose). n_parts > 1: owner-major rows.
+static int covis_front(ottohip_ctx* ctx, const ottohip_events* ev, const ottohip_covis_params* params,
+                       const int32_t* file_ids, int n_parts, Front& F, hipStream_t s) {
+  ++ctx->gen;
+  const int64_t E = ev->n_events;
+  F.E = E; F.Sn = ev->n_sessions;
+  F.P = 0; F.Rn = 0;
+  if (E == 0 || F.Sn == 0) return 0;
+  RowsPlan P;
+  OH_TRY(rows_plan(ctx, F.Lt, params->n_items, n_parts, s, P));
+  OH_TRY(front_prep_count(ctx, ev, params, file_ids, F, P, s));
+
+  const int ph = ctx->begin("rows", s, 0);
+  OH_TRY(rows_owner_keys(F, P, n_parts, s));
+  // fused layout: the sort's first pass drops the keys without a row entry (events without pairs; grouped: members),
+  // the later passes and the builders run over the En kept entries
+  uint32_t *rks = F.rk, *poss = F.pos;
+  int64_t En = E;
+  const SortSkip skip{P.fused ? (1u << P.cshift) - 1u : 0u, P.INV, &En};
+  bool bucketed = false;
+  if (P.try_bucket) {
+    const uint64_t* dstart = nullptr;
+    int ntl = 0;
+    OH_TRY(radix_skip_pass(ctx, F.rk, F.rk2, F.pos2, E, s, skip, &dstart, &ntl));
+    rks = F.rk2; poss = F.pos2;
+    if (En > RB_MIN_ENTRIES) OH_TRY(rows_bucket(ctx, F, P, s, rks, poss, F.rk, F.pos, En, dstart, ntl, &bucketed));
+    // not taken (few entries, or 2^32 words or more): the sort's remaining passes
+    if (!bucketed) OH_TRY(radix_sort_pairs(ctx, rks, poss, F.rk, F.pos, En, P.kbits, s, false, nullptr, 8));
+  } else {
+    OH_TRY(radix_sort_pairs(ctx, rks, poss, F.rk2, F.pos2, E, P.kbits, s, P.fused, P.fused ? &skip : nullptr));
+  }
+  if (!bucketed) {
+    if (P.fused) OH_TRY(rows_fused_sorted(ctx, F, P, s, rks, poss, En));
+    else OH_TRY(rows_unfused(ctx, F, P, s, rks, poss));
+  }
   ctx->end(ph, s);
   return 0;
 }

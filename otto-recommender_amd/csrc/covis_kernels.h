@@ -1183,13 +1183,11 @@ __global__ __launch_bounds__(RT_T) void k_rows_sums(const uint32_t* __restrict__
   if (threadIdx.x == 0) sums[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
 }
 
-// poff32 != null: u32 offsets, only for events with position in [plo, plo + pw) (windows of the event
-// range, one launch each, measured slower than one pass: plo = 0, pw = ~0); rows only when write_rows.
+// the word offsets go to wsorted (sorted order, u32) when given, else to poff32 (u32) when given, else to poff
 __global__ __launch_bounds__(RT_T) void k_rows_tile(const uint32_t* __restrict__ rks, const uint32_t* __restrict__ poss,
                                                     const uint32_t* __restrict__ cnt, int64_t n, uint32_t kmask,
                                                     uint32_t INV, int shift, const uint64_t* __restrict__ offs,
                                                     uint64_t* __restrict__ poff, uint32_t* __restrict__ poff32,
-                                                    uint32_t plo, uint32_t pw, int write_rows,
                                                     uint32_t* __restrict__ row_key, uint64_t* __restrict__ row_begin,
                                                     uint32_t* __restrict__ wsorted = nullptr) {
   const int64_t base = (int64_t)blockIdx.x * RT_TILE + (int64_t)threadIdx.x * RT_I;
@@ -1218,11 +1216,11 @@ __global__ __launch_bounds__(RT_T) void k_rows_tile(const uint32_t* __restrict__
       const uint32_t ps = poss[base + i];
       if (wsorted) {
       } else if (poff32) {
-        if (ps - plo < pw) poff32[ps] = (uint32_t)woff;
+        poff32[ps] = (uint32_t)woff;
       } else {
         poff[ps] = woff;
       }
-      if (st[i] && write_rows) {
+      if (st[i]) {
         const uint64_t r = run & 0xFFFFFFull;
         row_key[r] = key[i];
         row_begin[r] = woff;
@@ -1266,24 +1264,6 @@ __global__ __launch_bounds__(256) void k_link_fix(const uint32_t* __restrict__ l
       if (poff32) poff32[e] = (uint32_t)(o[j] + (lk[j] & LK_GMASK));
       else poff[e] = o[j] + (lk[j] & LK_GMASK);
     }
-}
-// XCD-aware form: block b runs on XCD b % 8 (workgroups are dealt round robin) and XCD x writes only the
-// slices (position high-bit digits) d = x (mod 8), one after the other, its blocks splitting each slice: a
-// destination line is written through ONE L2, where its 4-B writes merge before the line goes to HBM (from
-// eight XCDs a line went out in parts: 6.85 GB written per build for 0.88 GB of offsets). dstart[d * ntiles]
-// = the first element of slice d (radix_pass' offsets); gridDim.x % 8 == 0.
-__global__ __launch_bounds__(256) void k_poff_scatter_xcd(const uint32_t* __restrict__ pos,
-                                                          const uint32_t* __restrict__ woff, int64_t n,
-                                                          const uint64_t* __restrict__ dstart, int ntiles,
-                                                          uint32_t* __restrict__ poff32) {
-  const int x = blockIdx.x & 7, j = blockIdx.x >> 3, nj = gridDim.x >> 3;
-  for (int d = x; d < 256; d += 8) {
-    const int64_t a = (int64_t)dstart[(int64_t)d * ntiles];
-    const int64_t b = d + 1 < 256 ? (int64_t)dstart[(int64_t)(d + 1) * ntiles] : n;
-    const int64_t per = (b - a + nj - 1) / nj;
-    const int64_t s0 = a + (int64_t)j * per, s1 = s0 + per < b ? s0 + per : b;
-    for (int64_t k = s0 + threadIdx.x; k < s1; k += 256) poff32[pos[k]] = woff[k];
-  }
 }
 
 // ---- bucketed LDS counting sort of the row entries (fused layout, one GPU, keys of at most 23 bits). The sort's
@@ -1483,62 +1463,6 @@ __global__ __launch_bounds__(PL_T) void k_poff_scatter_lds(const uint32_t* __res
   }
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < np; i += PL_T) poff32[p0 + i] = img[i];
-}
-
-// ---- rows without a sort (OTTOHIP_ROWS=atomic, one GPU): the row of key k is the dense index k of
-// (type << A | aid); its words are cut into RA_SUB sub-ranges, one per counter, so the atomics of a hot
-// row spread over RA_SUB addresses. Each event takes its run inside its sub-range with one returning
-// atomic (word order inside a row is free: the reduce sorts it), one scan over the dense counters gives
-// every sub-range its first word, and the event's word offset is that start plus its rank.
-constexpr int RA_SUB = 8;
-__device__ __forceinline__ uint32_t ra_sub(int64_t e) { return (uint32_t)(e >> 8) & (RA_SUB - 1); }
-// RA_PER events per thread (coalesced, stride blockDim): their returning atomics are in flight together
-// (one at a time leaves the kernel bound by the atomics' round-trip latency)
-constexpr int RA_PER = 8;
-__global__ __launch_bounds__(256) void k_rows_atomic(const uint32_t* __restrict__ rk, const uint32_t* __restrict__ cnt,
-                                                     int64_t n, uint32_t kmask, uint32_t INV, uint32_t* __restrict__ dcnt,
-                                                     uint32_t* __restrict__ rank) {
-  const int64_t e0 = (int64_t)blockIdx.x * (256 * RA_PER) + threadIdx.x;
-  uint32_t key[RA_PER], c[RA_PER], r[RA_PER];
-#pragma unroll
-  for (int j = 0; j < RA_PER; ++j) {
-    const int64_t e = e0 + j * 256;
-    key[j] = e < n ? rk[e] & kmask : INV;
-    c[j] = key[j] != INV ? cnt[e] : 0u;
-  }
-#pragma unroll
-  for (int j = 0; j < RA_PER; ++j)
-    r[j] = c[j] ? atomicAdd(&dcnt[(uint64_t)key[j] * RA_SUB + ra_sub(e0 + j * 256)], c[j]) : 0u;
-#pragma unroll
-  for (int j = 0; j < RA_PER; ++j)
-    if (e0 + j * 256 < n) rank[e0 + j * 256] = r[j];
-}
-// word offset of every event (u32 when P < 2^32, else u64) from its sub-range start and rank
-__global__ __launch_bounds__(256) void k_rows_atomic_off(const uint32_t* __restrict__ rk, int64_t n, uint32_t kmask,
-                                                         uint32_t INV, const uint64_t* __restrict__ doff,
-                                                         const uint32_t* __restrict__ rank,
-                                                         uint32_t* __restrict__ poff32, uint64_t* __restrict__ poff) {
-  const int64_t e0 = (int64_t)blockIdx.x * (256 * RA_PER) + threadIdx.x;
-  uint64_t o[RA_PER];
-#pragma unroll
-  for (int j = 0; j < RA_PER; ++j) {
-    const int64_t e = e0 + j * 256;
-    const uint32_t key = e < n ? rk[e] & kmask : INV;
-    o[j] = key != INV ? doff[(uint64_t)key * RA_SUB + ra_sub(e)] + rank[e] : 0;
-  }
-#pragma unroll
-  for (int j = 0; j < RA_PER; ++j) {
-    const int64_t e = e0 + j * 256;
-    if (e < n) { if (poff32) poff32[e] = (uint32_t)o[j]; else poff[e] = o[j]; }
-  }
-}
-// dense rows: row r = key r, first word = its first sub-range's start
-__global__ void k_rows_dense(const uint64_t* __restrict__ doff, int64_t nk, uint32_t* __restrict__ row_key,
-                             uint64_t* __restrict__ row_begin) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= nk) return;
-  row_key[r] = (uint32_t)r;
-  row_begin[r] = doff[(uint64_t)r * RA_SUB];
 }
 
 // multi-GPU layout: row keys become (owner(aid), type, aid) so every owner's rows and words

@@ -4,7 +4,8 @@ Every case is counted twice in one process, with the default rows path and with 
 both results are compared with the per-file tables of the CPU oracle and with each other: the five tables in
 (aid, aid_next) order, all four per-rule statistics and the table digests. Every comparison is bit-exact (integer
 work). The bucketed path applies to more than 1024 row entries with keys of at most 23 bits; the cases say on which
-side of that they are."""
+side of that they are. The case "unfused" and test_wide_offsets reach the two fallbacks behind the sort: the unfused
+layout on one GPU and the 64-bit word offsets."""
 import functools
 import os
 
@@ -99,6 +100,10 @@ def _case_rows(name):
     if name == "bits24":  # 22 aid bits, 24-bit keys: the sort path
         pool = np.concatenate([[0, 255, 2 ** 21 - 1, 2 ** 21], rng.integers(0, 2 ** 21 + 1, 64)])
         return _random_sessions(rng, 2500, pool), 2 ** 21 + 1, 2
+    if name == "unfused":  # 3 * n_items >= 2^24: the rows no longer fit the fused layout's 24-bit row index, so one
+        # GPU takes the unfused layout (k_gather_counts, two scans, k_rows); 1 rule + 23 aid + 1 file bits per word
+        pool = np.concatenate([[0, 255, 256, 2 ** 23 - 1], rng.integers(0, 2 ** 23, 64)])
+        return _random_sessions(rng, 2500, pool), 2 ** 23, 2
     raise KeyError(name)
 
 
@@ -163,7 +168,7 @@ def _check(name, env=None):
 
 
 @pytest.mark.parametrize("name", ["edges", "small_catalogue", "one_bucket", "few_entries", "no_pairs", "one_entry",
-                                  "bits24"])
+                                  "bits24", "unfused"])
 def test_rows_match_sort_and_oracle(gpu, name):
     ref = _check(name)
     if name == "edges":  # the construction: rows of aid 0 and of the largest aid in all three types
@@ -190,6 +195,15 @@ def test_other_outlets(gpu, switch):
     take the sort path's partition pass and scatter (PART)."""
     _check("edges", {switch: "1"})
     _check("hub", {switch: "1"})
+
+
+def test_wide_offsets(gpu):
+    """OTTOHIP_POFF32=0 (read per call): 64-bit word offsets from k_rows_tile, through k_link_fix (grouped entries)
+    and into the emit, the path of a build with 2^32 words or more. The hub keeps the saturated count byte and the
+    link array in play."""
+    _check("edges", {"OTTOHIP_POFF32": "0"})
+    for g in ("1", "0"):
+        _check("hub", {"OTTOHIP_POFF32": "0", "OTTOHIP_GROUP": g})
 
 
 def test_out_of_range_aid(gpu):
