@@ -577,6 +577,62 @@ int ottohip_knn_topk_exact(ottohip_ctx* ctx, const ottohip_knn_index* index, con
                            int64_t n_q, int k, int32_t* out_idx, float* out_d2,
                            ottohip_knn_exact_stats* stats, void* stream);
 
+/* ---- Rank (model/rank.py): LightGBM booster scoring and the per-session top-k --------------
+ * One forest's raw arrays as the text model file holds them (train_lgbm_rankers.load_lgbm), trees
+ * concatenated: tree t has ni = tree_off[t + 1] - tree_off[t] internal nodes at [tree_off[t], tree_off[t + 1])
+ * of the node arrays and ni + 1 leaves at leaf_value[tree_off[t] + t ...]; a one-leaf tree has ni = 0.
+ * split_feature holds column indices (the order of col_dtype), not the model's own feature numbers. A child
+ * c >= 0 is internal node c of the tree, c < 0 is its leaf ~c. All arrays are HOST arrays. */
+typedef struct ottohip_forest {
+  int32_t n_trees;
+  const int32_t* tree_off;       /* [n_trees + 1], tree_off[0] = 0 */
+  const int32_t* split_feature;
+  const double* threshold;
+  const int32_t* decision_type;  /* bit 0 categorical (rejected), bit 1 default left, bits 2-3 missing type */
+  const int32_t* left_child;
+  const int32_t* right_child;
+  const double* leaf_value;
+} ottohip_forest;
+typedef struct ottohip_ranker ottohip_ranker;
+/* Validates, lowers and flattens n_forests (1..64) forests over columns of dtype codes col_dtype[n_cols] (the
+ * codes of ottohip_feature_columns) and uploads them. Every threshold is lowered against its column's dtype so
+ * that the device's native compare is the same predicate as LightGBM's double compare (ottohip_rank_lower).
+ * OTTOHIP_EINVAL: a categorical split, a missing type of 3, a threshold or leaf value that is not finite, a child
+ * outside its tree or reached twice, a column outside [0, n_cols). OTTOHIP_ELIMIT: the forests read more than
+ * 128 columns, or one forest has more than 2^19 nodes and leaves. */
+int ottohip_ranker_create(ottohip_ctx* ctx, const ottohip_forest* forests, int n_forests, const int* col_dtype,
+                          int n_cols, ottohip_ranker** out);
+void ottohip_ranker_free(ottohip_ranker* ranker);
+/* forests, columns read by any split, forests whose flattened form is kept in LDS by the scoring kernel, and that
+ * kernel's LDS bytes per workgroup; any output may be NULL */
+int ottohip_ranker_info(const ottohip_ranker* ranker, int* n_forests, int* n_used, int* n_resident,
+                        int64_t* lds_bytes);
+/* Booster.predict of model/rank.py:50 (raw scores) for every forest in one pass over the frame: cols[n_cols]
+ * (host array of device pointers, the ranker's column order; n_rows values each, of the column's dtype) ->
+ * scores (device, [n_forests x n_rows] float64): 0.0 + the leaf of tree 0 + the leaf of tree 1 + ... in tree
+ * order, IEEE float64. OTTOHIP_EINVAL: a column read by a forest has a NULL pointer. */
+int ottohip_ranker_predict(ottohip_ctx* ctx, const ottohip_ranker* ranker, void* const* cols, int n_cols,
+                           int64_t n_rows, double* scores, void* stream);
+/* model/rank.py:53-57: per session and forest, the k best rows by score descending (-0.0 ranks as 0.0; ties to
+ * the earlier row), 1 <= k <= 64. scores [n_forests x n_rows] and aid_next [n_rows] cover the candidates of
+ * n_sessions sessions; cand_off [n_sessions + 1] (device) are their offsets, taken relative to cand_off[0] (a
+ * slice of a longer offset array serves a session range). Writes out_off [n_sessions + 1] = prefix sums of
+ * min(k, candidates of the session), and for forest f at f * out_cap + out_off[s] + r the session's index s,
+ * aid_next, pred_score and pred_rank = r + 1. out_cap (entries per forest of the four outputs) >=
+ * min(n_rows, n_sessions * k). */
+int ottohip_ranker_topk(ottohip_ctx* ctx, const double* scores, int n_forests, int64_t n_rows,
+                        const int64_t* cand_off, int64_t n_sessions, const int32_t* aid_next, int k,
+                        int64_t out_cap, int64_t* out_off, int32_t* out_session, int32_t* out_aid_next,
+                        double* out_score, int16_t* out_rank, void* stream);
+/* The lowering of one split, no GPU call: (threshold, decision_type) on a column of dtype code dtype -> the
+ * int32 threshold key, flags (1: the key INT32_MIN -- a staged NaN, or that integer -- goes left; 2: the node
+ * has the zero band; 4: the band goes left) and the band's key range. A value's key is itself (integer
+ * columns) or the order-preserving map of its float32 bits, b ^ ((b >> 31) & 0x7fffffff), NaN -> INT32_MIN.
+ * The split sends key k left iff (k == INT32_MIN ? flag 1 : (flag 2 and band_lo <= k <= band_hi) ? flag 4 :
+ * k <= key). OTTOHIP_EINVAL for a split ottohip_ranker_create rejects. */
+int ottohip_rank_lower(double threshold, int decision_type, int dtype, int32_t* key, int* flags, int32_t* band_lo,
+                       int32_t* band_hi);
+
 /* Test hooks for the device primitives the engine is built from (parity tests only). */
 int ottohip_test_exclusive_scan_u32(ottohip_ctx* ctx, const uint32_t* in, uint64_t* out, int64_t n,
                                     uint64_t* total_host, void* stream);

@@ -6,3 +6,5 @@ function names and file contracts; compute runs in hand-written gfx950 HIP kerne
 behind the C-ABI in include/ottohip.h (libottohip.so).
 """
 __version__ = "0.1.0"
+
+from . import rank  # noqa: E402,F401  (the rank stage: parse_booster, Ranker, rank_files, submission_frame)

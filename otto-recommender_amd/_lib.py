@@ -66,6 +66,12 @@ class KnnExactStats(ctypes.Structure):
 KNN_CENTER = 1  # OTTOHIP_KNN_CENTER
 
 
+class Forest(ctypes.Structure):
+    _fields_ = [("n_trees", ctypes.c_int32), ("tree_off", ctypes.c_void_p), ("split_feature", ctypes.c_void_p),
+                ("threshold", ctypes.c_void_p), ("decision_type", ctypes.c_void_p), ("left_child", ctypes.c_void_p),
+                ("right_child", ctypes.c_void_p), ("leaf_value", ctypes.c_void_p)]
+
+
 # name -> (restype, argtypes); the exported symbol set of include/ottohip.h
 _VP, _I32, _I64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
 SIGNATURES = {
@@ -179,6 +185,16 @@ SIGNATURES = {
                                                    _VP]),
     "ottohip_knn_topk_exact": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.c_int, _VP, _VP,
                                               ctypes.POINTER(KnnExactStats), _VP]),
+    "ottohip_ranker_create": (ctypes.c_int, [_VP, ctypes.POINTER(Forest), ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                             ctypes.c_int, ctypes.POINTER(_VP)]),
+    "ottohip_ranker_free": (None, [_VP]),
+    "ottohip_ranker_info": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                           ctypes.POINTER(ctypes.c_int), ctypes.POINTER(_I64)]),
+    "ottohip_ranker_predict": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, _I64, _VP, _VP]),
+    "ottohip_ranker_topk": (ctypes.c_int, [_VP, _VP, ctypes.c_int, _I64, _VP, _I64, _VP, ctypes.c_int, _I64, _VP, _VP,
+                                           _VP, _VP, _VP, _VP]),
+    "ottohip_rank_lower": (ctypes.c_int, [ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_I32),
+                                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
     "ottohip_test_exclusive_scan_u32": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.POINTER(ctypes.c_uint64), _VP]),
     "ottohip_test_radix_sort_pairs": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.c_int, _VP]),
     "ottohip_test_lanes": (ctypes.c_int, [_VP, _VP, _VP]),

@@ -54,6 +54,9 @@ RETRIEVAL_FIRST_N_CO_COUNTS = {                             # config.py:90-96
 RETRIEVAL_CO_COUNTS_TO_JOIN = list(CO_EVENTS_TO_COUNT)      # config.py:98-104
 
 KEEP_TOP_K = 20                                             # config.py:31
+# the shape of the rankers rank.py scores (config.py:207-221; training itself is out of scope)
+PARAMS_LGBM = {"objective": "lambdarank", "n_estimators": 150, "learning_rate": 0.25, "max_depth": 4,
+               "num_leaves": 15}
 W2VEC_SEARCH_SIMILAR_FOR_FIRST_N_AIDS = 600_000             # config.py:109
 W2VEC_K = 20                                                # config.py:124
 W2VEC_VECTOR_SIZE = 100                                     # config.py:120
