@@ -633,6 +633,48 @@ int ottohip_ranker_topk(ottohip_ctx* ctx, const double* scores, int n_forests, i
 int ottohip_rank_lower(double threshold, int decision_type, int dtype, int32_t* key, int* flags, int32_t* band_lo,
                        int32_t* band_hi);
 
+/* ---- Downsample (model/downsample_retrieved.py) and submission recall (model/eval_submission.py) ----
+ * The draw, no GPU call: h = mix(mix(seed) ^ ((uint64)(uint32)session << 32 | (uint32)aid_next)) with
+ * mix(z): z += 0x9E3779B97F4A7C15; z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ * z ^= z >> 31 (uint64, wrapping). mix is a bijection, so rows with distinct (session, aid_next) have distinct h. */
+uint64_t ottohip_downsample_hash(uint64_t seed, int32_t session, int32_t aid_next);
+/* The select's path switch: a session with more rows than this ranks its negatives over global memory
+ * instead of LDS (same result). */
+int ottohip_downsample_lds_rows(void);
+/* model/downsample_retrieved.py:39-58 for up to three targets in one pass over a frame sorted by session.
+ * cand_off [n_sessions + 1] (device) are the sessions' row offsets, taken relative to cand_off[0]; session and
+ * aid_next [n_rows] (device) the frame's columns; targets[3] (HOST array of device pointers, int8 as
+ * ottohip_feature_columns reports them, values 0 or 1; a NULL entry skips the target). Per target t:
+ *   n_pos = positives of the session; a session without one is dropped;
+ *   max_n_neg = min(n_pos * keep_ratio_neg_to_pos, max_neg_per_session) in float64;
+ *   every positive is kept; a negative is kept iff random < max_n_neg, random = the negatives of its session
+ *   and target with a smaller h (ottohip_downsample_hash): min(n_neg, ceil(max_n_neg)) survive.
+ * out_off[t] (device, [n_sessions + 1]) = prefix sums of the kept rows per session, n_out[t] (host) their total,
+ * out_rows[t] (device, capacity out_cap) = the source row of every output row: per session the positives in
+ * frame order, then the kept negatives in frame order. out_rows == NULL: only out_off and n_out are written (a
+ * first call sizes the second's buffers). OTTOHIP_EINVAL before any launch: NULL cand_off, a negative or NaN
+ * ratio or cap; after the count: out_cap below a target's n_out. OTTOHIP_ELIMIT: 2^24 sessions or more in one call
+ * (pass the frame in session ranges: the draw does not depend on them). */
+int ottohip_downsample_plan(ottohip_ctx* ctx, const int64_t* cand_off, int64_t n_sessions, int64_t n_rows,
+                            const int32_t* session, const int32_t* aid_next, const int8_t* const* targets,
+                            double keep_ratio_neg_to_pos, double max_neg_per_session, uint64_t seed,
+                            int64_t* const* out_off, int64_t* const* out_rows, int64_t out_cap, int64_t* n_out,
+                            void* stream);
+/* dst_cols[c][o] = src_cols[c][rows[o]] for o < n_out and every column c < n_cols <= 128 in one launch.
+ * src_cols / dst_cols / col_dtype are HOST arrays (device pointers; dtype codes 0 int8, 1 int16, 2 int32,
+ * 3 float32, moved bit for bit); rows (device) holds indices into [0, n_src_rows). OTTOHIP_ERANGE: an index
+ * outside that range (read on the device; the outputs are then not valid). */
+int ottohip_gather_rows(ottohip_ctx* ctx, const void* const* src_cols, void* const* dst_cols, const int* col_dtype,
+                        int n_cols, const int64_t* rows, int64_t n_out, int64_t n_src_rows, void* stream);
+/* model/eval_submission.py:44-52 over one session universe of n_sessions sessions: labels and submitted aids
+ * as CSRs in the ottohip_labels_csr layout (off[t * (n_sessions + 1) + s] into the aid array; labels unique per
+ * (session, type), submitted aids as submitted, at most 64 per (session, type)). Per (session, type) with labels:
+ * hit = submitted entries that are labels, true = min(20, sum over labels of max(times submitted, 1)).
+ * sums_out[t * 2 + {0, 1}] = sum of hit, of true. OTTOHIP_EINVAL: a submitted list longer than 64. OTTOHIP_ELIMIT:
+ * 2^24 sessions or more in one call (the sums are additive over disjoint session sets). */
+int ottohip_submission_recall(ottohip_ctx* ctx, int64_t n_sessions, const int64_t* lab_off, const int32_t* lab_aid,
+                              const int64_t* sub_off, const int32_t* sub_aid, int64_t* sums_out, void* stream);
+
 /* Test hooks for the device primitives the engine is built from (parity tests only). */
 int ottohip_test_exclusive_scan_u32(ottohip_ctx* ctx, const uint32_t* in, uint64_t* out, int64_t n,
                                     uint64_t* total_host, void* stream);

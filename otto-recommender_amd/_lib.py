@@ -195,6 +195,14 @@ SIGNATURES = {
                                            _VP, _VP, _VP, _VP]),
     "ottohip_rank_lower": (ctypes.c_int, [ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_I32),
                                           ctypes.POINTER(ctypes.c_int), ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
+    "ottohip_downsample_hash": (ctypes.c_uint64, [ctypes.c_uint64, _I32, _I32]),
+    "ottohip_downsample_lds_rows": (ctypes.c_int, []),
+    "ottohip_downsample_plan": (ctypes.c_int, [_VP, _VP, _I64, _I64, _VP, _VP, ctypes.POINTER(_VP), ctypes.c_double,
+                                               ctypes.c_double, ctypes.c_uint64, ctypes.POINTER(_VP),
+                                               ctypes.POINTER(_VP), _I64, ctypes.POINTER(_I64), _VP]),
+    "ottohip_gather_rows": (ctypes.c_int, [_VP, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int),
+                                           ctypes.c_int, _VP, _I64, _I64, _VP]),
+    "ottohip_submission_recall": (ctypes.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, ctypes.POINTER(_I64), _VP]),
     "ottohip_test_exclusive_scan_u32": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.POINTER(ctypes.c_uint64), _VP]),
     "ottohip_test_radix_sort_pairs": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.c_int, _VP]),
     "ottohip_test_lanes": (ctypes.c_int, [_VP, _VP, _VP]),

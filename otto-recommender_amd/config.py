@@ -57,6 +57,8 @@ KEEP_TOP_K = 20                                             # config.py:31
 # the shape of the rankers rank.py scores (config.py:207-221; training itself is out of scope)
 PARAMS_LGBM = {"objective": "lambdarank", "n_estimators": 150, "learning_rate": 0.25, "max_depth": 4,
                "num_leaves": 15}
+DOWNSAMPLE_RATIO_NEG_TO_POS = 40                            # config.py:203 (negatives kept per positive)
+DOWNSAMPLE_MAX_NEG_PER_SESSION = 100                        # config.py:204
 W2VEC_SEARCH_SIMILAR_FOR_FIRST_N_AIDS = 600_000             # config.py:109
 W2VEC_K = 20                                                # config.py:124
 W2VEC_VECTOR_SIZE = 100                                     # config.py:120
