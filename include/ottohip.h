@@ -675,6 +675,104 @@ int ottohip_gather_rows(ottohip_ctx* ctx, const void* const* src_cols, void* con
 int ottohip_submission_recall(ottohip_ctx* ctx, int64_t n_sessions, const int64_t* lab_off, const int32_t* lab_aid,
                               const int64_t* sub_off, const int32_t* sub_aid, int64_t* sums_out, void* stream);
 
+/* ---- LambdaRank GBDT training (model/train_lgbm_rankers.py; DESIGN.md, train). The stages of one boosting
+ * iteration over a binned uint8 matrix [n_rows][stride] (row-major, feature f of row r at r * stride + f). Every
+ * float64 result is the IEEE result of a stated sequence of + - * / (the unit is compiled without contraction),
+ * every histogram an integer sum, so results do not depend on the launch shape. */
+/* Host-built float64 tables (device pointers) and the objective's parameters: the kernels compute no exp or log.
+ *   gain[31] label gains; disc[10000] = 1 / log2(2 + r); sig[n_sig]: entry i = 1 / (1 + exp(sigma * d_i)) over
+ *   [sig_min, sig_max], looked up at trunc((d - sig_min) * sig_factor), clamped at both ends; log2t[4097] =
+ *   log2(0.5 + i / 8192); inv_max_dcg[n_sessions]. */
+typedef struct {
+  const double* gain;
+  const double* disc;
+  const double* sig;
+  const double* log2t;
+  const double* inv_max_dcg;
+  int64_t n_sig;
+  double sig_min, sig_max, sig_factor, sigma;
+  int32_t truncation_level, norm;
+} ottohip_train_tables;
+/* The gradient kernel's path switch: a session with more rows than this keeps its sorted rows in a global scratch
+ * instead of LDS (same result). */
+int ottohip_train_lds_rows(void);
+/* Bins one column (dtype code of ottohip_feature_columns: 0 int8, 1 int16, 2 int32, 3 float32) into feature
+ * `feature` of the matrix: bin = the number of bounds[0, n_bounds) (device, ascending float64) below the value as
+ * float64, so value <= bounds[b] <=> bin <= b. n_bounds <= 255. */
+int ottohip_train_bin_column(ottohip_ctx* ctx, const void* col, int dtype, int64_t n_rows, const double* bounds,
+                             int n_bounds, uint8_t* bins, int stride, int feature, void* stream);
+/* LambdaRank gradients and hessians of every session (off [n_sessions + 1], relative to off[0]) from float64
+ * scores and int8 labels in [0, 30]: per session the rows sorted by score descending (stable, -0.0 == 0.0), every
+ * pair of positions (i, j), i < j, i < truncation_level, with different labels; a row adds its partners in
+ * ascending partner position. g, h (device, [n_rows]) are overwritten. OTTOHIP_ELIMIT: a session of more than
+ * 10,000 rows; OTTOHIP_ERANGE: a label outside [0, 30]. */
+int ottohip_train_gradients(ottohip_ctx* ctx, const double* scores, const int8_t* labels, const int64_t* off,
+                            int64_t n_sessions, int64_t n_rows, const ottohip_train_tables* tables, double* g,
+                            double* h, void* stream);
+/* Fixed point with a power-of-two scale: max|g| = m * 2^e_g (frexp), q_g = rint(g * 2^(15 - e_g)) (half to even,
+ * |q_g| <= 2^15), likewise h with e_h; gh (device, [n_rows][2] int32) = (q_g, q_h). *all_zero = max|g| == 0. */
+int ottohip_train_quantise(ottohip_ctx* ctx, const double* g, const double* h, int64_t n_rows, int32_t* gh, int* e_g,
+                           int* e_h, int* all_zero, void* stream);
+/* Histogram of the rows rows[0, n) (device int32 row indices into the matrix of n_total rows) over the k drawn
+ * features feats (device int32): hist (device, [k][256][3] int64, overwritten) = (sum q_g, sum q_h, count) per bin.
+ * max_blocks > 0 caps the workgroups per feature group (one workgroup then flushes its int32 partials every 2^15
+ * rows); 0: the device's default. OTTOHIP_ERANGE: a row or feature index outside the matrix. */
+int ottohip_train_histogram(ottohip_ctx* ctx, const uint8_t* bins, int stride, int64_t n_total, const int32_t* gh,
+                            const int32_t* rows, int64_t n, const int32_t* feats, int k, int64_t* hist, int max_blocks,
+                            void* stream);
+/* Best split "bin <= b" of each of n_hist * k histograms ([n_hist][k][256][3]; n_bins [k] device int32): both child
+ * counts >= min_child_samples, both hessian sums >= min_sum_hessian, gain = GL^2 / (HL + l2) + GR^2 / (HR + l2) -
+ * G^2 / (H + l2) > 0 with real sums = integer sums * 2^(e - 15); larger gain, then smaller b. records (device,
+ * [n_hist * k][8] int64) = {gain (float64 bits), b or -1, Qg left, Qh left, count left, Qg, Qh, count}. */
+int ottohip_train_split_scan(ottohip_ctx* ctx, const int64_t* hist, int n_hist, int k, const int32_t* n_bins, int e_g,
+                             int e_h, int64_t min_child_samples, double min_sum_hessian, double lambda_l2,
+                             int64_t* records, void* stream);
+/* Stable partition of a row list: rows_out (another buffer) = the rows with bin[feature] <= bin in their order,
+ * then the others in their order; *n_left (host) = the former's count. */
+int ottohip_train_partition(ottohip_ctx* ctx, const uint8_t* bins, int stride, int64_t n_total, int feature, int bin,
+                            const int32_t* rows, int64_t n, int32_t* rows_out, int64_t* n_left, void* stream);
+/* scores[r] += leaf_value[leaf of row r]: the tree (device arrays; LightGBM's numbering, a child < 0 is leaf ~child;
+ * split_feature indexes the matrix, a row goes left iff bin <= split_bin) walked on the binned matrix. */
+int ottohip_train_apply(ottohip_ctx* ctx, const uint8_t* bins, int stride, int64_t n_rows, const int32_t* split_feature,
+                        const int32_t* split_bin, const int32_t* left_child, const int32_t* right_child,
+                        const double* leaf_value, int n_leaves, double* scores, void* stream);
+/* NDCG@k (k <= 64) per session with the gradient kernel's sort: out[s] = (sum over the first k positions, in
+ * position order, of gain[label] * disc[position]) * inv_max_dcg[s], or 1.0 where inv_max_dcg[s] is 0. */
+int ottohip_train_ndcg(ottohip_ctx* ctx, const double* scores, const int8_t* labels, const int64_t* off,
+                       int64_t n_sessions, int64_t n_rows, const double* gain, const double* disc,
+                       const double* inv_max_dcg, int k, double* out, void* stream);
+
+/* The trainer: the boosting loop behind an opaque handle. The feature draw, the leaf choice from the split records
+ * and the leaves' row-list segments live on the host side of the library; a tree costs the host one read of the root's
+ * records, one read of 2 k records per split that needs its children's histograms, and per iteration the quantiser's
+ * exponents and the error flags. */
+typedef struct {
+  int32_t num_leaves, max_depth;      /* max_depth <= 0: no limit */
+  int64_t min_child_samples;
+  double min_sum_hessian, lambda_l2, learning_rate, colsample_bytree;
+  uint64_t seed;
+} ottohip_train_params;
+typedef struct ottohip_trainer ottohip_trainer;
+/* bins [n_rows][stride], labels, off [n_sessions + 1] and the tables' arrays are device memory the caller keeps alive
+ * for the handle's life; n_bins [n_features] (host) the features' bin counts (a feature with one bin is never drawn).
+ * Scores start at 0.0. OTTOHIP_ELIMIT: a session of more than 10,000 rows; OTTOHIP_ERANGE: a label outside [0, 30]. */
+int ottohip_trainer_create(ottohip_ctx* ctx, const uint8_t* bins, int stride, int64_t n_rows, const int32_t* n_bins,
+                           int n_features, const int8_t* labels, const int64_t* off, int64_t n_sessions,
+                           const ottohip_train_tables* tables, const ottohip_train_params* params,
+                           ottohip_trainer** out);
+/* One iteration: gradients, quantiser, the tree's feature draw, leaf-wise growth, scores += the leaves' values.
+ * *n_leaves = the new tree's leaves, or 0 when no tree was added (max|g| == 0 or no valid split): training ends. */
+int ottohip_trainer_boost(ottohip_trainer* trainer, int* n_leaves, void* stream);
+/* The last tree into host arrays of cap_leaves - 1 internal nodes and cap_leaves leaves (LightGBM's numbering;
+ * split_feature indexes the matrix, a row goes left iff bin <= split_bin); *n_leaves = its leaves. */
+int ottohip_trainer_tree(const ottohip_trainer* trainer, int cap_leaves, int32_t* split_feature, int32_t* split_bin,
+                         double* split_gain, int32_t* left_child, int32_t* right_child, double* internal_value,
+                         double* internal_weight, int64_t* internal_count, double* leaf_value, double* leaf_weight,
+                         int64_t* leaf_count, int* n_leaves);
+/* Copies the training scores (device, [n_rows] float64) to scores (device). */
+int ottohip_trainer_scores(const ottohip_trainer* trainer, double* scores, void* stream);
+void ottohip_trainer_free(ottohip_trainer* trainer);
+
 /* Test hooks for the device primitives the engine is built from (parity tests only). */
 int ottohip_test_exclusive_scan_u32(ottohip_ctx* ctx, const uint32_t* in, uint64_t* out, int64_t n,
                                     uint64_t* total_host, void* stream);

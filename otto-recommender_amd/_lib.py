@@ -72,6 +72,19 @@ class Forest(ctypes.Structure):
                 ("right_child", ctypes.c_void_p), ("leaf_value", ctypes.c_void_p)]
 
 
+class TrainTables(ctypes.Structure):
+    _fields_ = [("gain", ctypes.c_void_p), ("disc", ctypes.c_void_p), ("sig", ctypes.c_void_p),
+                ("log2t", ctypes.c_void_p), ("inv_max_dcg", ctypes.c_void_p), ("n_sig", ctypes.c_int64),
+                ("sig_min", ctypes.c_double), ("sig_max", ctypes.c_double), ("sig_factor", ctypes.c_double),
+                ("sigma", ctypes.c_double), ("truncation_level", ctypes.c_int32), ("norm", ctypes.c_int32)]
+
+
+class TrainParams(ctypes.Structure):
+    _fields_ = [("num_leaves", ctypes.c_int32), ("max_depth", ctypes.c_int32), ("min_child_samples", ctypes.c_int64),
+                ("min_sum_hessian", ctypes.c_double), ("lambda_l2", ctypes.c_double), ("learning_rate", ctypes.c_double),
+                ("colsample_bytree", ctypes.c_double), ("seed", ctypes.c_uint64)]
+
+
 # name -> (restype, argtypes); the exported symbol set of include/ottohip.h
 _VP, _I32, _I64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
 SIGNATURES = {
@@ -203,6 +216,29 @@ SIGNATURES = {
     "ottohip_gather_rows": (ctypes.c_int, [_VP, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int),
                                            ctypes.c_int, _VP, _I64, _I64, _VP]),
     "ottohip_submission_recall": (ctypes.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, ctypes.POINTER(_I64), _VP]),
+    "ottohip_train_lds_rows": (ctypes.c_int, []),
+    "ottohip_train_bin_column": (ctypes.c_int, [_VP, _VP, ctypes.c_int, _I64, _VP, ctypes.c_int, _VP, ctypes.c_int,
+                                                ctypes.c_int, _VP]),
+    "ottohip_train_gradients": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I64, _I64, ctypes.POINTER(TrainTables), _VP, _VP,
+                                               _VP]),
+    "ottohip_train_quantise": (ctypes.c_int, [_VP, _VP, _VP, _I64, _VP, ctypes.POINTER(ctypes.c_int),
+                                              ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _VP]),
+    "ottohip_train_histogram": (ctypes.c_int, [_VP, _VP, ctypes.c_int, _I64, _VP, _VP, _I64, _VP, ctypes.c_int, _VP,
+                                               ctypes.c_int, _VP]),
+    "ottohip_train_split_scan": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int,
+                                                _I64, ctypes.c_double, ctypes.c_double, _VP, _VP]),
+    "ottohip_train_partition": (ctypes.c_int, [_VP, _VP, ctypes.c_int, _I64, ctypes.c_int, ctypes.c_int, _VP, _I64,
+                                               _VP, ctypes.POINTER(_I64), _VP]),
+    "ottohip_train_apply": (ctypes.c_int, [_VP, _VP, ctypes.c_int, _I64, _VP, _VP, _VP, _VP, _VP, ctypes.c_int, _VP,
+                                           _VP]),
+    "ottohip_train_ndcg": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _VP, ctypes.c_int, _VP, _VP]),
+    "ottohip_trainer_create": (ctypes.c_int, [_VP, _VP, ctypes.c_int, _I64, ctypes.POINTER(_I32), ctypes.c_int, _VP, _VP,
+                                              _I64, ctypes.POINTER(TrainTables), ctypes.POINTER(TrainParams),
+                                              ctypes.POINTER(_VP)]),
+    "ottohip_trainer_boost": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_int), _VP]),
+    "ottohip_trainer_tree": (ctypes.c_int, [_VP, ctypes.c_int] + [_VP] * 11 + [ctypes.POINTER(ctypes.c_int)]),
+    "ottohip_trainer_scores": (ctypes.c_int, [_VP, _VP, _VP]),
+    "ottohip_trainer_free": (None, [_VP]),
     "ottohip_test_exclusive_scan_u32": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.POINTER(ctypes.c_uint64), _VP]),
     "ottohip_test_radix_sort_pairs": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.c_int, _VP]),
     "ottohip_test_lanes": (ctypes.c_int, [_VP, _VP, _VP]),

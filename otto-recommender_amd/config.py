@@ -54,9 +54,17 @@ RETRIEVAL_FIRST_N_CO_COUNTS = {                             # config.py:90-96
 RETRIEVAL_CO_COUNTS_TO_JOIN = list(CO_EVENTS_TO_COUNT)      # config.py:98-104
 
 KEEP_TOP_K = 20                                             # config.py:31
-# the shape of the rankers rank.py scores (config.py:207-221; training itself is out of scope)
-PARAMS_LGBM = {"objective": "lambdarank", "n_estimators": 150, "learning_rate": 0.25, "max_depth": 4,
-               "num_leaves": 15}
+# the rankers train.py fits and rank.py scores (config.py:207-221). subsample has no effect: without a bagging
+# frequency LightGBM does not bag, and the reference sets none
+PARAMS_LGBM = {"objective": "lambdarank", "boosting_type": "gbdt", "metric": "ndcg", "n_estimators": 150,
+               "learning_rate": 0.25, "max_depth": 4, "num_leaves": 15, "colsample_bytree": 0.25, "subsample": 0.50,
+               "min_child_samples": 20, "importance_type": "gain", "seed": 42}
+PARAMS_LGBM_FIT = {"eval_at": [20], "verbose": 25}          # config.py:223-227
+# what the reference leaves to LightGBM 3.3.4's defaults, restated FROM MEMORY (lightgbm is not installed, nothing
+# here was checked against it): unpinned. label_gain None: 2^l - 1 for l = 0..30
+PARAMS_LGBM_DEFAULTS = {"max_bin": 255, "min_sum_hessian_in_leaf": 1e-3, "lambda_l2": 0.0, "lambda_l1": 0.0,
+                        "sigmoid": 1.0, "lambdarank_truncation_level": 30, "lambdarank_norm": True, "label_gain": None,
+                        "subsample_freq": 0}
 DOWNSAMPLE_RATIO_NEG_TO_POS = 40                            # config.py:203 (negatives kept per positive)
 DOWNSAMPLE_MAX_NEG_PER_SESSION = 100                        # config.py:204
 W2VEC_SEARCH_SIMILAR_FOR_FIRST_N_AIDS = 600_000             # config.py:109
