@@ -357,7 +357,8 @@ static bool env_is(const char* name, const char* value) {
 struct RowsPlan {
   bool fused = false;
   bool owner_local = false;  // n_parts > 1: (owner, type, the aid's index among its owner's aids) below the count byte
-  bool group = false;        // one sort entry per (session, type, aid) with pairs; OTTOHIP_GROUP=0: one per event
+  bool group = false;        // one sort entry per (session, type, aid) with pairs (the default off the bucketed
+                             // path; OTTOHIP_GROUP=1 / 0: everywhere / nowhere), else one per event
   bool try_bucket = false;   // rows_bucket: one GPU, keys of at most 23 bits, u32 offsets; OTTOHIP_ROWS=sort: the sort
   bool wide = false;         // OTTOHIP_POFF32=0: u64 word offsets although the words are fewer than 2^32
   bool prep_v1 = false;      // OTTOHIP_PREP=v1: the first body of the fused S1+S2 kernel
@@ -383,9 +384,12 @@ static int rows_plan(ottohip_ctx* ctx, const Layout& Lt, int32_t n_items, int n_
     P.owner_local = ((uint64_t)n_parts << (P.om_lb + 2)) < (1ull << P.cshift);
   }
   P.fused = fits && (n_parts == 1 || P.owner_local);
-  P.group = P.fused && !env_is("OTTOHIP_GROUP", "0");
   P.wide = env_is("OTTOHIP_POFF32", "0");
   P.try_bucket = P.fused && n_parts == 1 && P.kbits <= 23 && !env_is("OTTOHIP_ROWS", "sort") && !P.wide;
+  // grouped entries pay where the sort's later passes run over them (the sort and owner-local paths); the bucketed
+  // rows cost the same either way, so there the grouping hash of S2 and k_link_fix are left out. When rows_bucket
+  // declines at run time the call finishes on the sort with single entries. OTTOHIP_GROUP=1 / 0 forces either.
+  P.group = P.fused && (env_is("OTTOHIP_GROUP", "1") || (!env_is("OTTOHIP_GROUP", "0") && !P.try_bucket));
   P.prep_v1 = env_is("OTTOHIP_PREP", "v1");
   P.bucket_direct = env_is("OTTOHIP_ROWS_DIRECT", "1");
   P.bucket_part = env_is("OTTOHIP_ROWS_PART", "1");
@@ -518,8 +522,9 @@ static int front_prep_count(ottohip_ctx* ctx, const ottohip_events* ev, const ot
     k_prep_count<<<(unsigned)NB, 64, 0, s>>>(off, F.first, NB, ev->aid, ev->ts, ev->type, F.evp, params->n_items,
                                              params->dedup, F.err, R, Lt.A, F.cnt, rk, pos_w, cs, F.link);
   else
-    k_prep_count2<<<(unsigned)NB, 64, 0, s>>>(off, F.first, NB, ev->aid, ev->ts, ev->type, F.evp, params->n_items,
-                                              params->dedup, F.err, R, prep_plan(R), Lt.A, F.cnt, rk, pos_w, cs, F.link);
+    (P.group ? k_prep_count2<true> : k_prep_count2<false>)<<<(unsigned)NB, 64, 0, s>>>(
+        off, F.first, NB, ev->aid, ev->ts, ev->type, F.evp, params->n_items, params->dedup, F.err, R, prep_plan(R),
+        Lt.A, F.cnt, rk, pos_w, cs, F.link);
   if (hipGetLastError() != hipSuccess) { set_error("k_prep_count launch failed"); return OTTOHIP_EHIP; }
   int32_t nl = 0;
   OH_TRY(d2h(&nl, n_long, 1, s));
@@ -701,10 +706,10 @@ static int covis_emit_words(ottohip_ctx* ctx, const Front& F, const ottohip_even
                            : k_emit<false, false, true>);
   if (F.NB > 0)
     ek<<<(unsigned)F.NB, 64, 0, s>>>(F.off, F.first, F.NB, F.evp, F.R, F.Lt, F.fb, ev->n_files, F.fid, F.cnt,
-                                         EvOff{F.poff, F.poff32, nullptr}, w0, eerr, dbg);
+                                         EvOff{F.poff, F.poff32}, w0, eerr, dbg);
   if (F.nl > 0)
     k_emit_long<<<F.nl, 64, 0, s>>>(F.off, F.long_list, F.d_loff, F.lscr, F.lpscr, F.evp, F.R, F.Lt, F.fb,
-                                     ev->n_files, F.fid, F.cnt, EvOff{F.poff, F.poff32, nullptr}, w0);
+                                     ev->n_files, F.fid, F.cnt, EvOff{F.poff, F.poff32}, w0);
   if (hipGetLastError() != hipSuccess) { set_error("k_emit launch failed"); return OTTOHIP_EHIP; }
   ctx->end(ph, s);
   int herr = 0;

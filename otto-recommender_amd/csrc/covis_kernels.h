@@ -750,6 +750,8 @@ __device__ __forceinline__ void prep_group_rows(LDS& S, const uint32_t (&cv)[PB_
 //                         lanes predicated by type; the symmetric rule of the lane's type is scanned once, after the
 //                         loop; with dedup on the identity run is 1
 // Rules with a window that is not around 0, or beyond the PP_WIN distinct ones, search the whole session as before.
+// GROUP (template parameter): grouped row entries, link written; the single-entry instantiation holds no per-chunk
+// counts, no grouping hash and no link store (link is not read).
 constexpr int PP_WIN = 2;
 struct PrepPlan {
   int32_t n_rules;
@@ -796,6 +798,7 @@ __device__ __forceinline__ void seg_bounds(const uint64_t* key, int idx, int64_t
 #endif
 }
 
+template <bool GROUP>
 __global__ __launch_bounds__(64) void k_prep_count2(const int64_t* __restrict__ off, const int64_t* __restrict__ first,
                                                     int64_t NB, const int32_t* __restrict__ aid,
                                                     const int32_t* __restrict__ ts, const int8_t* __restrict__ ty,
@@ -1002,9 +1005,12 @@ __global__ __launch_bounds__(64) void k_prep_count2(const int64_t* __restrict__ 
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     // ---- partner counts and row keys (chunks downwards: cb = the first break after the chunk)
-    uint32_t cv[NCH];  // grouped rows: the counts of the lane's events (c is wave-uniform: a select per chunk)
+    // grouped rows: the counts of the lane's events (c is wave-uniform: a select per chunk); !GROUP: never touched
+    [[maybe_unused]] uint32_t cv[NCH];
+    if constexpr (GROUP) {
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) cv[c] = 0u;
+      for (int c = 0; c < NCH; ++c) cv[c] = 0u;
+    }
     int cb0 = nb_ev, cb1 = nb_ev;
 #pragma unroll 1
     for (int c = nch - 1; c >= 0; --c) {
@@ -1082,7 +1088,7 @@ __global__ __launch_bounds__(64) void k_prep_count2(const int64_t* __restrict__ 
       if (mb1) cb1 = c * 64 + (int)__builtin_ctzll(mb1);
       if (in) {
         cnt[E0 + idx] = cn;
-        if (link) {
+        if constexpr (GROUP) {
 #pragma unroll
           for (int j = 0; j < NCH; ++j)
             if (j == c) cv[j] = cn;
@@ -1094,7 +1100,7 @@ __global__ __launch_bounds__(64) void k_prep_count2(const int64_t* __restrict__ 
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    if (link) prep_group_rows(S, cv, l, nch, nb_ev, E0, A, INV, cshift, rk, link);
+    if constexpr (GROUP) prep_group_rows(S, cv, l, nch, nb_ev, E0, A, INV, cshift, rk, link);
     b += nsess;
   }
 }
@@ -1105,15 +1111,9 @@ __global__ __launch_bounds__(64) void k_prep_count2(const int64_t* __restrict__ 
 struct EvOff {
   const uint64_t* p64;
   const uint32_t* p32;
-  const uint32_t* link;  // grouped row entries (LK_REP): a member's run follows from its rep's offset; null: none
-  __device__ __forceinline__ uint64_t at(int64_t e) const { return p32 ? (uint64_t)p32[e] : p64[e]; }
-  // the first word of event e's run (e has pairs)
-  __device__ __forceinline__ uint64_t run(int64_t e) const {
-    if (!link) return at(e);
-    const uint32_t lk = link[e];
-    if (lk & LK_REP) return at(e);
-    return at(e + (int64_t)(lk >> LK_DSHIFT) - 512) + (lk & LK_GMASK);
-  }
+  // the first word of event e's run (e has pairs). Grouped row entries: k_link_fix has set the members' offsets, so
+  // the emit kernels read one offset per event in either layout and never see the link array
+  __device__ __forceinline__ uint64_t run(int64_t e) const { return p32 ? (uint64_t)p32[e] : p64[e]; }
 };
 
 __global__ void k_gather_counts(const uint32_t* __restrict__ rk, const uint32_t* __restrict__ pos,
