@@ -773,6 +773,53 @@ int ottohip_trainer_tree(const ottohip_trainer* trainer, int cap_leaves, int32_t
 int ottohip_trainer_scores(const ottohip_trainer* trainer, double* scores, void* stream);
 void ottohip_trainer_free(ottohip_trainer* trainer);
 
+/* ---- Word2Vec trainer (model/w2vec_aids.py:56-70): CBOW with negative sampling, synchronous mini-batches --------
+ * The definition is DESIGN.md "Word2Vec trainer"; tests/w2v_oracle.py restates it in numpy and the kernels match it
+ * bit for bit. All positions of a batch read the weights as they stood at its start; every update is rounded to
+ * int64 fixed point (2^shift), clamped so that no sum can wrap, and added with integer atomics, so a fit does not
+ * depend on the order of execution. Limits: dim <= 128, window <= 31, negative <= 32. */
+typedef struct {
+  int32_t dim, window, negative;
+  int32_t n_sig;            /* entries of the sigmoid table over [-max_exp, max_exp) */
+  int32_t epochs, shift;    /* fixed point: 2^shift */
+  int64_t batch_positions;  /* B; also sets the clamp of one contribution */
+  uint64_t seed;
+  double alpha, min_alpha, max_exp;
+  uint32_t type_mask;       /* bit t: events of type t are read */
+} ottohip_w2v_params;
+typedef struct ottohip_w2v ottohip_w2v;
+/* One epoch's compaction: the events whose type is in type_mask, whose aid has a row (row_of_aid [n_items], device,
+ * -1 = none, rows < n_vocab) and whose keep draw (seed, epoch, event index) is <= keep_thr[row] (device uint32
+ * [n_vocab]), in order. Outputs (device, capacity n_events; offsets n_sessions + 1): rows, orig (the event index),
+ * sid (the session) per kept event and offsets, the sentence of session s = kept positions [offsets[s],
+ * offsets[s + 1]). *n_kept (host) through one host read. */
+int ottohip_w2v_compact(ottohip_ctx* ctx, const ottohip_events* ev, const int32_t* row_of_aid, int32_t n_items,
+                        const uint32_t* keep_thr, int64_t n_vocab, uint32_t type_mask, uint64_t seed, int32_t epoch,
+                        int32_t* rows, int32_t* orig, int32_t* sid, int64_t* offsets, int64_t* n_kept, void* stream);
+/* One batch, the kept positions [b0, b1) of a compaction, from the caller's weights (device [n_vocab][dim]): ADDS
+ * the fixed-point contributions into acc0 (syn0) and acc1 (syn1neg), device int64 [n_vocab][dim], and sets flag0 /
+ * flag1 (device uint8 [n_vocab]) of the rows it touched. cum: the 31-bit cumulative negative table (device uint32
+ * [n_vocab], cum[n_vocab - 1] == 2^31); sig: the sigmoid table (device float [n_sig]); lr: the batch's rate. */
+int ottohip_w2v_batch(ottohip_ctx* ctx, const int32_t* rows, const int32_t* orig, const int32_t* sid,
+                      const int64_t* offsets, int64_t n_kept, int64_t n_sessions, int64_t b0, int64_t b1,
+                      const float* syn0, const float* syn1neg, int64_t n_vocab, const uint32_t* cum, const float* sig,
+                      const ottohip_w2v_params* params, int32_t epoch, float lr, long long* acc0, long long* acc1,
+                      uint8_t* flag0, uint8_t* flag1, void* stream);
+/* weights[r] += (float)((double)acc[r] * 2^-shift) on the rows whose flag is set; their acc and flag are zeroed. */
+int ottohip_w2v_apply(ottohip_ctx* ctx, float* weights, long long* acc, uint8_t* flag, int64_t n_vocab, int dim,
+                      int shift, void* stream);
+/* The trainer: ev, row_of_aid, keep_thr, cum and sig are device memory the caller keeps alive for the handle's life;
+ * syn0_init (device [n_vocab][dim]) is copied, syn1neg starts at 0. ottohip_w2v_epoch runs epoch e (0 .. epochs - 1,
+ * in order): compaction, then per batch the batch kernel and the apply pass, the batch's rate
+ * max(min_alpha, alpha - (alpha - min_alpha) * (e + b * B / n_kept) / epochs) in float64, passed as float. */
+int ottohip_w2v_create(ottohip_ctx* ctx, const ottohip_events* ev, const int32_t* row_of_aid, int32_t n_items,
+                       const uint32_t* keep_thr, const uint32_t* cum, int64_t n_vocab, const float* sig,
+                       const float* syn0_init, const ottohip_w2v_params* params, ottohip_w2v** out);
+int ottohip_w2v_epoch(ottohip_w2v* w2v, int32_t epoch, int64_t* n_kept, int64_t* n_batches, void* stream);
+/* Copies syn0 (and syn1neg unless NULL) to device buffers [n_vocab][dim]. */
+int ottohip_w2v_vectors(const ottohip_w2v* w2v, float* syn0, float* syn1neg, void* stream);
+void ottohip_w2v_free(ottohip_w2v* w2v);
+
 /* Test hooks for the device primitives the engine is built from (parity tests only). */
 int ottohip_test_exclusive_scan_u32(ottohip_ctx* ctx, const uint32_t* in, uint64_t* out, int64_t n,
                                     uint64_t* total_host, void* stream);

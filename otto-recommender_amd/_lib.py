@@ -85,6 +85,13 @@ class TrainParams(ctypes.Structure):
                 ("colsample_bytree", ctypes.c_double), ("seed", ctypes.c_uint64)]
 
 
+class W2vParams(ctypes.Structure):
+    _fields_ = [("dim", ctypes.c_int32), ("window", ctypes.c_int32), ("negative", ctypes.c_int32),
+                ("n_sig", ctypes.c_int32), ("epochs", ctypes.c_int32), ("shift", ctypes.c_int32),
+                ("batch_positions", ctypes.c_int64), ("seed", ctypes.c_uint64), ("alpha", ctypes.c_double),
+                ("min_alpha", ctypes.c_double), ("max_exp", ctypes.c_double), ("type_mask", ctypes.c_uint32)]
+
+
 # name -> (restype, argtypes); the exported symbol set of include/ottohip.h
 _VP, _I32, _I64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
 SIGNATURES = {
@@ -239,6 +246,16 @@ SIGNATURES = {
     "ottohip_trainer_tree": (ctypes.c_int, [_VP, ctypes.c_int] + [_VP] * 11 + [ctypes.POINTER(ctypes.c_int)]),
     "ottohip_trainer_scores": (ctypes.c_int, [_VP, _VP, _VP]),
     "ottohip_trainer_free": (None, [_VP]),
+    "ottohip_w2v_compact": (ctypes.c_int, [_VP, ctypes.POINTER(Events), _VP, _I32, _VP, _I64, ctypes.c_uint32,
+                                           ctypes.c_uint64, _I32, _VP, _VP, _VP, _VP, ctypes.POINTER(_I64), _VP]),
+    "ottohip_w2v_batch": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _I64, _I64, _I64, _I64, _VP, _VP, _I64, _VP, _VP,
+                                         ctypes.POINTER(W2vParams), _I32, ctypes.c_float, _VP, _VP, _VP, _VP, _VP]),
+    "ottohip_w2v_apply": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I64, ctypes.c_int, ctypes.c_int, _VP]),
+    "ottohip_w2v_create": (ctypes.c_int, [_VP, ctypes.POINTER(Events), _VP, _I32, _VP, _VP, _I64, _VP, _VP,
+                                          ctypes.POINTER(W2vParams), ctypes.POINTER(_VP)]),
+    "ottohip_w2v_epoch": (ctypes.c_int, [_VP, _I32, ctypes.POINTER(_I64), ctypes.POINTER(_I64), _VP]),
+    "ottohip_w2v_vectors": (ctypes.c_int, [_VP, _VP, _VP, _VP]),
+    "ottohip_w2v_free": (None, [_VP]),
     "ottohip_test_exclusive_scan_u32": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.POINTER(ctypes.c_uint64), _VP]),
     "ottohip_test_radix_sort_pairs": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.c_int, _VP]),
     "ottohip_test_lanes": (ctypes.c_int, [_VP, _VP, _VP]),

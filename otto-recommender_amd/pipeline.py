@@ -80,6 +80,20 @@ def _knn_lists(words, emb, knn_queries, ctx, dev, group, exact=False):
     return q_aid.contiguous(), nb.contiguous(), rk.contiguous()
 
 
+def train_embeddings(events, n_items: int | None = None, ctx=None, **params):
+    """The two Word2Vec models run() reads, trained on the device from the events (covis.DeviceEvents or host
+    Events; the reference trains on the train and test sessions together, config.W2VEC_MODELS): returns
+    (words_all, emb_all, words_12, emb_12), the all-types model and the carts+orders one, each as its vocabulary in
+    index_to_key order and its vectors. params: w2vec.train_w2vec_model's (default: the reference's
+    vector_size=100, window=10, min_count=5)."""
+    from .w2vec import train_w2vec_model, _device_events
+    ev = _device_events(events)
+    p = {"vector_size": config.W2VEC_VECTOR_SIZE, "window": 10, "min_count": 5, **params}
+    m_all = train_w2vec_model(ev, types=[0, 1, 2], n_items=n_items, ctx=ctx, **p)
+    m_12 = train_w2vec_model(ev, types=[1, 2], n_items=n_items, ctx=ctx, **p)
+    return m_all.wv.index_to_key, m_all.wv.vectors, m_12.wv.index_to_key, m_12.wv.vectors
+
+
 def run(train, test, labels, words_all, emb_all, words_12, emb_12, n_items: int = config.N_ITEMS_OTTO,
         n_clusters: int = 50, kmeans_iter: int = 100, knn_queries: int = config.W2VEC_SEARCH_SIMILAR_FOR_FIRST_N_AIDS,
         ctx=None, timings: dict | None = None, keep_tables: bool = False, group=None, n_init="auto",

@@ -8,8 +8,8 @@ The index scans every row (bf16 MFMA scores keep 24 candidates per query, an exa
 them; see csrc/knn.hip): a true neighbour is certain to be returned when fewer than 24 other rows come
 within the bf16 scores' error of it (DESIGN.md §5 kNN states the bound and the envelope in which this is
 an exact search: embeddings centred near the origin, not tightly clustered). The reference's faiss
-IVFFlat (nlist 100, nprobe 3) probes 3 of 100 lists. Word2Vec training (gensim) is out of
-scope: embeddings are an input (a vocabulary `words` in index_to_key order + vectors).
+IVFFlat (nlist 100, nprobe 3) probes 3 of 100 lists. The embeddings are an input of these functions (a
+vocabulary `words` in index_to_key order + vectors); train_w2vec_model below produces them on the device.
 
 That default search is exact inside the envelope only. `exact=True` (KnnIndex.search and every function
 below) is exact for every input: the index is packed centred (`center=True`), the main pass keeps every row
@@ -26,6 +26,7 @@ import numpy as np
 
 from . import _lib
 from . import config
+from .train import MASK64, mix  # splitmix64's finaliser: the draw of csrc/downsample.hip, train.hip and w2v.hip
 
 
 class KnnIndex:
@@ -183,3 +184,343 @@ def retrieve_w2vec_knns_via_faiss_index(embeddings, words, k: int | None = None,
         os.makedirs(os.path.dirname(cache_file) or ".", exist_ok=True)
         df.to_parquet(cache_file)
     return df
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Training (model/w2vec_aids.py:18-70): CBOW with negative sampling as synchronous mini-batches on the device.
+# DESIGN.md "Word2Vec trainer" is the definition; csrc/w2v.hip runs it. The functions below that take numpy
+# arrays are host plumbing (vocabulary, tables, initial weights) and need no GPU.
+W2V_MAX_DIM, W2V_MAX_WINDOW, W2V_MAX_NEGATIVE = 128, 31, 32
+
+
+def draw(seed: int, epoch: int, slot: int, index: int) -> int:
+    """The trainer's counter-based draw: slot 0 keep, 1 reduced window, 2 + j negative j; index: the event's place
+    in the CSR, so no draw depends on the compaction or on the batch size."""
+    return mix(mix(mix(int(seed) & MASK64) ^ ((int(epoch) << 32) | int(slot))) ^ int(index))
+
+
+def _mix_np(z):
+    """mix over a uint64 array"""
+    from .synth import _mix
+    with np.errstate(over="ignore"):
+        return _mix(np.asarray(z, np.uint64) + np.uint64(0x9E3779B97F4A7C15))
+
+
+def vocabulary(counts_by_aid, min_count: int = 5):
+    """(index_to_key, counts) from the per-aid event counts: the aids with count >= min_count, by count descending,
+    ties by aid ascending."""
+    c = np.asarray(counts_by_aid, np.int64)
+    keys = np.flatnonzero(c >= max(int(min_count), 1))
+    cnt = c[keys]
+    order = np.lexsort((keys, -cnt))
+    return keys[order].astype(np.int64), cnt[order].astype(np.int64)
+
+
+def keep_thresholds(counts, sample: float = 1e-3) -> np.ndarray:
+    """uint32 of the kept probability (sqrt(c / (sample T)) + 1) (sample T) / c capped at 1, T the kept words' total
+    count: an event is kept when the high 32 bits of its draw are <= the threshold. sample = 0 keeps everything."""
+    counts = np.asarray(counts, np.float64)
+    if sample <= 0:
+        return np.full(len(counts), 0xFFFFFFFF, np.uint32)
+    if sample > 1:
+        raise ValueError("sample: a share of the corpus in [0, 1]")
+    tc = float(sample) * float(counts.sum())
+    p = (np.sqrt(counts / tc) + 1.0) * (tc / counts)
+    thr = np.minimum(np.floor(np.minimum(p, 1.0) * 4294967296.0), 4294967295.0)
+    return np.where(p >= 1.0, 4294967295.0, thr).astype(np.uint32)
+
+
+def negative_table(counts, ns_exponent: float = 0.75) -> np.ndarray:
+    """31-bit cumulative table of count^ns_exponent (uint32 [V], last entry 2^31): a 31-bit draw x picks the first
+    row whose entry is > x."""
+    cs = np.cumsum(np.asarray(counts, np.float64) ** float(ns_exponent))
+    cum = np.rint(cs / cs[-1] * 2147483648.0)
+    cum[-1] = 2147483648.0
+    return cum.astype(np.uint32)
+
+
+def sigmoid_table(n_sig: int = config.W2VEC_SIGMOID_ENTRIES, max_exp: float = config.W2VEC_MAX_EXP) -> np.ndarray:
+    """fp32 sigmoid at the n_sig left edges of equal cells of [-max_exp, max_exp)"""
+    x = (np.arange(n_sig, dtype=np.float64) / n_sig * 2.0 - 1.0) * max_exp
+    return (1.0 / (1.0 + np.exp(-x))).astype(np.float32)
+
+
+def initial_weights(seed: int, n_vocab: int, dim: int) -> np.ndarray:
+    """syn0[r][d] = (u - 0.5) / dim in fp32, u the top 24 bits of a draw on (seed, r, d) times 2^-24"""
+    sm = mix(int(seed) & MASK64)
+    out = np.empty((n_vocab, dim), np.float32)
+    r = np.arange(n_vocab, dtype=np.uint64)
+    for d in range(dim):
+        u = _mix_np(np.uint64(mix(sm ^ ((0xFFFFFFFF << 32) | d))) ^ r) >> np.uint64(40)
+        out[:, d] = (u.astype(np.float32) * np.float32(2.0 ** -24) - np.float32(0.5)) / np.float32(dim)
+    return out
+
+
+def _type_mask(types) -> int:
+    if types is None:
+        return 0b111
+    m = 0
+    for t in types:
+        t = config.TYPE2ID.get(t, t) if isinstance(t, str) else t
+        if not 0 <= int(t) < 3:
+            raise ValueError(f"types: {t!r} is not an event type")
+        m |= 1 << int(t)
+    return m
+
+
+def _device_events(events):
+    from .covis import DeviceEvents
+    return events if isinstance(events, DeviceEvents) else DeviceEvents.from_host(events)
+
+
+def load_sessions_as_sentences(events, types=None):
+    """w2vec_aids.py:18-39 over resident events: a pandas DataFrame [session (index in the CSR), n_aid, sentence] with
+    one row per session that has an event of `types` (None = all), the sentence its aids in event order."""
+    import pandas as pd
+    import torch
+    ev = _device_events(events)
+    mask = _type_mask(types)
+    ty = ev.type.to(torch.int64)
+    keep = ((torch.tensor(mask, device=ty.device) >> ty) & 1).bool()
+    lens = ev.offsets[1:] - ev.offsets[:-1]
+    sid = torch.repeat_interleave(torch.arange(ev.n_sessions, device=ty.device), lens)[keep]
+    aid = ev.aid[keep].cpu().numpy()
+    cnt = torch.bincount(sid, minlength=ev.n_sessions).cpu().numpy()
+    has = np.flatnonzero(cnt)
+    cuts = np.cumsum(cnt[has])[:-1]
+    return pd.DataFrame({"session": has.astype(np.int64), "n_aid": cnt[has].astype(np.uint16),
+                         "sentence": np.split(aid, cuts) if len(has) else []})
+
+
+class KeyedVectors:
+    """The two attributes the reference reads of gensim's: index_to_key (aids, most frequent first) and vectors."""
+
+    def __init__(self, index_to_key, vectors):
+        self.index_to_key = np.asarray(index_to_key, np.int64)
+        self.vectors = np.ascontiguousarray(vectors, np.float32)
+
+
+class Word2VecModel:
+    """A trained model: .wv.index_to_key, .wv.vectors, .params, .save(path) (an .npz of its own, not gensim's pickle)."""
+
+    def __init__(self, index_to_key, vectors, params: dict | None = None):
+        self.wv = KeyedVectors(index_to_key, vectors)
+        self.params = dict(params or {})
+
+    def save(self, path: str):
+        import json
+        os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
+        with open(path, "wb") as f:  # a file object: numpy appends no suffix to the name
+            np.savez(f, index_to_key=self.wv.index_to_key, vectors=self.wv.vectors,
+                     params=np.frombuffer(json.dumps(self.params, sort_keys=True).encode(), np.uint8))
+
+    @staticmethod
+    def load(path: str) -> "Word2VecModel":
+        import json
+        with np.load(path) as z:
+            return Word2VecModel(z["index_to_key"], z["vectors"], json.loads(bytes(z["params"]).decode()))
+
+
+def _w2v_params(params: dict) -> dict:
+    p = dict(config.W2VEC_DEFAULTS)
+    p.update({"vector_size": config.W2VEC_VECTOR_SIZE, "window": 5, "min_count": 5, "workers": 1,
+              "batch_positions": config.W2VEC_BATCH_POSITIONS})
+    unknown = set(params) - set(p)
+    if unknown:
+        raise TypeError(f"train_w2vec_model: unknown parameters {sorted(unknown)}")
+    p.update(params)
+    if p["sg"] != 0:
+        raise NotImplementedError("sg=1 (skip-gram) is not supported: the trainer is CBOW")
+    if p["hs"] != 0:
+        raise NotImplementedError("hs=1 (hierarchical softmax) is not supported: the trainer samples negatives")
+    if p["cbow_mean"] != 1:
+        raise NotImplementedError("cbow_mean=0 is not supported: the context is averaged")
+    if not p["shrink_windows"]:
+        raise NotImplementedError("shrink_windows=False is not supported: every position draws its window")
+    if not 1 <= int(p["vector_size"]) <= W2V_MAX_DIM:
+        raise ValueError(f"vector_size: 1..{W2V_MAX_DIM} (two dims per lane of a wave)")
+    if not 1 <= int(p["window"]) <= W2V_MAX_WINDOW:
+        raise ValueError(f"window: 1..{W2V_MAX_WINDOW} (a window's rows sit one per lane)")
+    if not 1 <= int(p["negative"]) <= W2V_MAX_NEGATIVE:
+        raise ValueError(f"negative: 1..{W2V_MAX_NEGATIVE}")
+    if int(p["epochs"]) < 1 or int(p["batch_positions"]) < 1:
+        raise ValueError("epochs and batch_positions: at least 1")
+    return p
+
+
+def w2v_abi_params(p: dict, type_mask: int = 0b111) -> "_lib.W2vParams":
+    return _lib.W2vParams(dim=int(p["vector_size"]), window=int(p["window"]), negative=int(p["negative"]),
+                          n_sig=int(p.get("n_sig", config.W2VEC_SIGMOID_ENTRIES)), epochs=int(p["epochs"]),
+                          shift=int(p.get("shift", config.W2VEC_FIXED_SHIFT)),
+                          batch_positions=int(p["batch_positions"]), seed=int(p["seed"]) & MASK64,
+                          alpha=float(p["alpha"]), min_alpha=float(p["min_alpha"]),
+                          max_exp=float(p.get("max_exp", config.W2VEC_MAX_EXP)), type_mask=int(type_mask))
+
+
+class Word2VecTrainer:
+    """The device trainer behind train_w2vec_model (ottohip_w2v_*): vocabulary and tables from the events, then
+    epoch(e) for e = 0 .. epochs - 1 in order, vectors() and free(). params: the resolved dict of _w2v_params."""
+
+    def __init__(self, events, types=None, n_items: int | None = None, ctx=None, params: dict | None = None):
+        import torch
+        p = self.params = _w2v_params(params or {})
+        self.types = None if types is None else list(types)
+        self.mask = _type_mask(types)
+        _lib.require_gpu()
+        ev = self.events = _device_events(events)
+        self.ctx = ctx or _lib.context()
+        dev = self.device = ev.aid.device
+        self.dim = int(p["vector_size"])
+        ty = ev.type.to(torch.int64)
+        sel = ((torch.tensor(self.mask, device=dev) >> ty) & 1).bool()
+        aid_sel = ev.aid[sel].to(torch.int64)
+        if aid_sel.numel() and int(aid_sel.min()) < 0:
+            raise ValueError("events: negative aid")
+        self.n_items = int(n_items) if n_items is not None else (int(ev.aid.max()) + 1 if ev.n_events else 0)
+        counts_by_aid = torch.bincount(aid_sel[aid_sel < self.n_items], minlength=self.n_items).cpu().numpy()
+        self.index_to_key, self.counts = vocabulary(counts_by_aid, p["min_count"])
+        V = self.n_vocab = len(self.index_to_key)
+        self.h = ctypes.c_void_p()
+        if V == 0:
+            return
+        row_of_aid = np.full(self.n_items, -1, np.int32)
+        row_of_aid[self.index_to_key] = np.arange(V, dtype=np.int32)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        # device arrays the handle reads for its whole life (uint32 tables travel as their int32 bits)
+        self.row_of_aid, self.keep_thr = up(row_of_aid), up(keep_thresholds(self.counts, p["sample"]).view(np.int32))
+        self.cum, self.sig = up(negative_table(self.counts, p["ns_exponent"]).view(np.int32)), up(sigmoid_table())
+        init = up(initial_weights(p["seed"], V, self.dim))
+        self._abi_ev, self.abi_params = ev.abi(), w2v_abi_params(p, self.mask)
+        _lib.check(_lib.load().ottohip_w2v_create(self.ctx.h, ctypes.byref(self._abi_ev), _lib.ptr(self.row_of_aid),
+                                                  self.n_items, _lib.ptr(self.keep_thr), _lib.ptr(self.cum), V,
+                                                  _lib.ptr(self.sig), _lib.ptr(init), ctypes.byref(self.abi_params),
+                                                  ctypes.byref(self.h)))
+
+    def epoch(self, e: int, stream=None):
+        """(kept positions, batches) of epoch e"""
+        nk, nb = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(_lib.load().ottohip_w2v_epoch(self.h, int(e), ctypes.byref(nk), ctypes.byref(nb),
+                                                 _lib.stream_handle(stream)))
+        return int(nk.value), int(nb.value)
+
+    def vectors(self, with_syn1neg: bool = False, stream=None):
+        """syn0 (and syn1neg) as device tensors [n_vocab, dim]"""
+        import torch
+        out = [torch.empty((self.n_vocab, self.dim), dtype=torch.float32, device=self.device)
+               for _ in range(2 if with_syn1neg else 1)]
+        if self.n_vocab:
+            _lib.check(_lib.load().ottohip_w2v_vectors(self.h, _lib.ptr(out[0]), _lib.ptr(out[1]) if with_syn1neg else None,
+                                                       _lib.stream_handle(stream)))
+        return tuple(out) if with_syn1neg else out[0]
+
+    def free(self):
+        if self.h:
+            _lib.load().ottohip_w2v_free(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def train_w2vec_model(events, types=None, n_items: int | None = None, ctx=None, stream=None, stats: dict | None = None,
+                      **params) -> Word2VecModel:
+    """w2vec_aids.py:56-70 on the device: Word2Vec(sentences, vector_size, window, min_count, ...) over the sessions of
+    `events` (covis.DeviceEvents, or host synth.Events) restricted to `types`. Parameters are gensim's names
+    (config.W2VEC_DEFAULTS; plus batch_positions); sg=1, hs=1 and cbow_mean=0 raise NotImplementedError, workers is
+    accepted and unused. Two calls with the same input return the same bytes. stats (optional dict) receives
+    n_kept / n_batches per epoch."""
+    t = Word2VecTrainer(events, types, n_items, ctx, params)
+    p = t.params
+    try:
+        for e in range(int(p["epochs"]) if t.n_vocab else 0):
+            nk, nb = t.epoch(e, stream)
+            if stats is not None:
+                stats.setdefault("n_kept", []).append(nk)
+                stats.setdefault("n_batches", []).append(nb)
+        vectors = t.vectors(stream=stream).cpu().numpy()
+    finally:
+        t.free()
+    return Word2VecModel(t.index_to_key, vectors, {k: p[k] for k in sorted(p)} | {"types": t.types})
+
+
+def get_model_file(model_name: str) -> str:
+    """w2vec_aids.py:42-43 (an .npz here)"""
+    return f"{config.DIR_ARTIFACTS}/word2vec/{model_name}.npz"
+
+
+def load_w2vec_model(path_or_name: str, events=None, types=None, use_cache: bool | None = None, **params) -> Word2VecModel:
+    """w2vec_aids.py:46-53: the cached model file when config.W2VEC_USE_CACHE and it exists, else a model trained
+    from `events` and saved there. A name of config.W2VEC_MODELS supplies the file (get_model_file), `types` and
+    the parameters; anything else is taken as the file's path."""
+    cfg = config.W2VEC_MODELS.get(path_or_name)
+    path = get_model_file(path_or_name) if cfg is not None else path_or_name
+    use_cache = config.W2VEC_USE_CACHE if use_cache is None else use_cache
+    if use_cache and os.path.exists(path):
+        return Word2VecModel.load(path)
+    if events is None:
+        raise FileNotFoundError(f"{path}: no cached model, and no events to train one from")
+    if cfg is not None:
+        types = cfg.get("types") if types is None else types
+        params = {**cfg["params"], **params}
+    model = train_w2vec_model(events, types=types, **params)
+    model.save(path)
+    return model
+
+
+def retrieve_w2vec_knns(model, k: int | None = None, first_n_aids: int | None = None, events=None, types=None,
+                        cache_file: str | None = None, exact: bool = False, **params):
+    """w2vec_aids.py:176-206 from the model on: `model` is a Word2VecModel, or a name / path for load_w2vec_model
+    (trained from `events` when no cached file exists). Neighbours of the first `first_n_aids` words as
+    get_top_k_similar_faiss returns them: [aid, aid_next, dist_w2vec, rank_w2vec]."""
+    if isinstance(model, str):
+        cfg = config.W2VEC_MODELS.get(model, {})
+        k = cfg.get("k") if k is None else k
+        first_n_aids = cfg.get("first_n_aids") if first_n_aids is None else first_n_aids
+        model = load_w2vec_model(model, events=events, types=types, **params)
+    return retrieve_w2vec_knns_via_faiss_index(model.wv.vectors, model.wv.index_to_key, k=k, first_n_aids=first_n_aids,
+                                               cache_file=cache_file, exact=exact)
+
+
+# ---- the trainer's stages on their own (parity tests, tools/w2v_timing.py): device tensors in and out
+def w2v_compact(events, row_of_aid, keep_thr, type_mask: int, seed: int, epoch: int, ctx=None, stream=None):
+    """One epoch's compaction (ottohip_w2v_compact): (rows, orig, sid, offsets) as device tensors cut to the kept
+    count; row_of_aid int32 [n_items] and keep_thr (uint32 bits, [n_vocab]) are device tensors."""
+    import torch
+    ev = _device_events(events)
+    ctx = ctx or _lib.context()
+    dev = ev.aid.device
+    n = max(ev.n_events, 1)
+    rows, orig, sid = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    off = torch.empty(ev.n_sessions + 1, dtype=torch.int64, device=dev)
+    nk = ctypes.c_int64()
+    abi_ev = ev.abi()
+    _lib.check(_lib.load().ottohip_w2v_compact(ctx.h, ctypes.byref(abi_ev), _lib.ptr(row_of_aid), int(row_of_aid.numel()),
+                                               _lib.ptr(keep_thr), int(keep_thr.numel()), int(type_mask),
+                                               int(seed) & MASK64, int(epoch), _lib.ptr(rows), _lib.ptr(orig),
+                                               _lib.ptr(sid), _lib.ptr(off), ctypes.byref(nk), _lib.stream_handle(stream)))
+    k = int(nk.value)
+    return rows[:k], orig[:k], sid[:k], off
+
+
+def w2v_batch(rows, orig, sid, offsets, b0: int, b1: int, syn0, syn1neg, cum, sig, abi_params, epoch: int, lr: float,
+              acc0, acc1, flag0, flag1, ctx=None, stream=None):
+    """The kept positions [b0, b1) from the given weights (ottohip_w2v_batch): adds into acc0 / acc1 (int64
+    [n_vocab, dim]) and sets flag0 / flag1 (uint8 [n_vocab]). All arguments are device tensors."""
+    ctx = ctx or _lib.context()
+    _lib.check(_lib.load().ottohip_w2v_batch(ctx.h, _lib.ptr(rows), _lib.ptr(orig), _lib.ptr(sid), _lib.ptr(offsets),
+                                             int(rows.numel()), int(offsets.numel()) - 1, int(b0), int(b1),
+                                             _lib.ptr(syn0), _lib.ptr(syn1neg), int(syn0.shape[0]), _lib.ptr(cum),
+                                             _lib.ptr(sig), ctypes.byref(abi_params), int(epoch), float(lr),
+                                             _lib.ptr(acc0), _lib.ptr(acc1), _lib.ptr(flag0), _lib.ptr(flag1),
+                                             _lib.stream_handle(stream)))
+
+
+def w2v_apply(weights, acc, flag, shift: int = config.W2VEC_FIXED_SHIFT, ctx=None, stream=None):
+    """weights += the fixed-point sums of the flagged rows, in place; sums and flags are zeroed (ottohip_w2v_apply)"""
+    ctx = ctx or _lib.context()
+    _lib.check(_lib.load().ottohip_w2v_apply(ctx.h, _lib.ptr(weights), _lib.ptr(acc), _lib.ptr(flag),
+                                             int(weights.shape[0]), int(weights.shape[1]), int(shift),
+                                             _lib.stream_handle(stream)))
