@@ -820,6 +820,33 @@ int ottohip_w2v_epoch(ottohip_w2v* w2v, int32_t epoch, int64_t* n_kept, int64_t*
 int ottohip_w2v_vectors(const ottohip_w2v* w2v, float* syn0, float* syn1neg, void* stream);
 void ottohip_w2v_free(ottohip_w2v* w2v);
 
+/* ETL: the OTTO jsonl files -> the integer columns of etl/jsonl_to_parquet.py:23-56, parsed on the device.
+ * text (device, 16-byte aligned) is a piece of a file: whole lines, n_bytes < 2^31 (OTTOHIP_ELIMIT above). A line is
+ * what stands between two '\n' (the last may lack its '\n'); n_lines counts all of them, blank ones too. The strict
+ * grammar (ETL): white space is ' ', '\t', '\r', numbers are 0 | [1-9][0-9]{0,17},
+ *   sessions line: { "session": int, "events": [ { "aid": int, "ts": int, "type": "clicks"|"carts"|"orders" }, ... ] }
+ *   labels line:   { "session": int, "labels": { "clicks"|"carts"|"orders": int | [ int, ... ], ... } }
+ * with the members of an object in any order, each once. kind: 0 sessions, 1 labels.
+ * ottohip_jsonl_count: *n_lines and *n_rows (HOST) of the piece, the sizes the parse calls need; nothing is
+ * validated here.
+ * ottohip_jsonl_sessions: one row per event in file order: session, aid, ts (ms / 1000), type (0 clicks, 1 carts,
+ * 2 orders). rows_per_line (device, may be NULL): the rows of every line, -1 for a blank line. cap_rows / cap_lines:
+ * the rows the column buffers and the entries rows_per_line hold; OTTOHIP_EINVAL before any write if the piece
+ * needs more. ottohip_jsonl_labels: one row per aid in order of appearance, a scalar value is one row.
+ * Any byte outside the grammar, an unknown, missing or repeated key: OTTOHIP_EINVAL; a number of more than 18
+ * digits, a session or aid above 2^31 - 1, ts / 1000 above 2^31 - 1: OTTOHIP_ELIMIT. ottohip_last_error() then names
+ * the 1-based line (line_base = lines of the file before this piece) and the first bad byte's offset in the
+ * piece; the outputs are not defined. ottohip_jsonl_tile_bytes: the bytes one wave classifies (tests). */
+int ottohip_jsonl_tile_bytes(void);
+int ottohip_jsonl_count(ottohip_ctx* ctx, const uint8_t* text, int64_t n_bytes, int kind, int64_t* n_lines,
+                        int64_t* n_rows, void* stream);
+int ottohip_jsonl_sessions(ottohip_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t line_base, int32_t* session,
+                           int32_t* aid, int32_t* ts, int8_t* type, int64_t* rows_per_line, int64_t cap_rows,
+                           int64_t cap_lines, void* stream);
+int ottohip_jsonl_labels(ottohip_ctx* ctx, const uint8_t* text, int64_t n_bytes, int64_t line_base, int32_t* session,
+                         int8_t* type, int32_t* aid, int64_t* rows_per_line, int64_t cap_rows, int64_t cap_lines,
+                         void* stream);
+
 /* Test hooks for the device primitives the engine is built from (parity tests only). */
 int ottohip_test_exclusive_scan_u32(ottohip_ctx* ctx, const uint32_t* in, uint64_t* out, int64_t n,
                                     uint64_t* total_host, void* stream);

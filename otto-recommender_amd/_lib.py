@@ -256,6 +256,11 @@ SIGNATURES = {
     "ottohip_w2v_epoch": (ctypes.c_int, [_VP, _I32, ctypes.POINTER(_I64), ctypes.POINTER(_I64), _VP]),
     "ottohip_w2v_vectors": (ctypes.c_int, [_VP, _VP, _VP, _VP]),
     "ottohip_w2v_free": (None, [_VP]),
+    "ottohip_jsonl_tile_bytes": (ctypes.c_int, []),
+    "ottohip_jsonl_count": (ctypes.c_int, [_VP, _VP, _I64, ctypes.c_int, ctypes.POINTER(_I64), ctypes.POINTER(_I64),
+                                           _VP]),
+    "ottohip_jsonl_sessions": (ctypes.c_int, [_VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _I64, _VP]),
+    "ottohip_jsonl_labels": (ctypes.c_int, [_VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _I64, _I64, _VP]),
     "ottohip_test_exclusive_scan_u32": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.POINTER(ctypes.c_uint64), _VP]),
     "ottohip_test_radix_sort_pairs": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.c_int, _VP]),
     "ottohip_test_lanes": (ctypes.c_int, [_VP, _VP, _VP]),
