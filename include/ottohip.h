@@ -847,6 +847,42 @@ int ottohip_jsonl_labels(ottohip_ctx* ctx, const uint8_t* text, int64_t n_bytes,
                          int8_t* type, int32_t* aid, int64_t* rows_per_line, int64_t cap_rows, int64_t cap_lines,
                          void* stream);
 
+/* Submission csv (model/submit.py:32-60): the ranked rows -> the bytes of the Kaggle file, on the device.
+ * Targets in the order clicks, carts, orders; session / aid_next / pred_rank / n_rows are HOST arrays of three
+ * entries, the pointers in them device columns of n_rows[t] rows in any order (NULL with n_rows[t] == 0: the target
+ * is absent). Rows with 1 <= pred_rank <= keep_top_k (in [1, 64]) are kept; every (session, target) with a kept row
+ * is the line "{session}_{target},{aid aid ...}\n", its aids in pred_rank order, equal ranks in input order; the lines
+ * follow the header "session_type,labels\n" in the order of their session_type strings.
+ * ottohip_submit_plan: sorts and sizes the file: *out the plan, *n_lines (data lines) and *n_bytes (header included),
+ * HOST. n_bad (HOST, three entries): rows with session < 0, with aid_next < 0, with pred_rank < 1; if there are any
+ * the call fails with OTTOHIP_EINVAL and no plan (n_bad is set). Fewer than 2^31 rows in all (OTTOHIP_ELIMIT).
+ * ottohip_submit_write: the file's bytes into out (device, 16-byte aligned, cap_bytes >= *n_bytes); no host read.
+ * The same bytes on every run. */
+typedef struct ottohip_submit ottohip_submit;
+int ottohip_submit_plan(ottohip_ctx* ctx, const int32_t* const* session, const int32_t* const* aid_next,
+                        const int16_t* const* pred_rank, const int64_t* n_rows, int keep_top_k, ottohip_submit** out,
+                        int64_t* n_lines, int64_t* n_bytes, int64_t* n_bad, void* stream);
+int ottohip_submit_write(ottohip_ctx* ctx, const ottohip_submit* plan, uint8_t* out, int64_t cap_bytes, void* stream);
+void ottohip_submit_free(ottohip_submit* plan);
+/* The reader: text (device, 16-byte aligned) is a piece of a submission csv, whole lines, n_bytes < 2^31; first: the
+ * piece opens the file and starts with the header line. The strict grammar (Submission csv):
+ *   file := "session_type,labels\n" line*     line := number "_" ("clicks"|"carts"|"orders") "," [number (" " number)*] "\n"
+ *   number := "0" | [1-9][0-9]*, at most 10 digits, at most 2147483647; the last line's "\n" may be missing.
+ * ottohip_submission_scan: *n_lines (data lines), n_rows (three entries: submitted aids per target), *targets (bit t:
+ * a line of target t is present) and *error (~0: none so far; else offset << 8 | reason of the first bad line head),
+ * all HOST; numbers are not validated here.
+ * ottohip_submission_parse: one row per submitted aid in file order per target: session[t], aid_next[t] (HOST arrays
+ * of device pointers, cap_rows[t] rows each; OTTOHIP_EINVAL before any write if a target needs more). With session
+ * NULL nothing is written and the call only validates. The first byte outside the grammar: OTTOHIP_EINVAL, a number of
+ * more than 10 digits or above 2^31 - 1: OTTOHIP_ELIMIT; ottohip_last_error() then reads
+ * "submission_parse: line L, byte B: reason" with L = line_base + the 1-based line of the piece and B = byte_base +
+ * the offset in the piece (the smallest bad offset wins); the outputs are not defined. */
+int ottohip_submission_scan(ottohip_ctx* ctx, const uint8_t* text, int64_t n_bytes, int first, int64_t* n_lines,
+                            int64_t* n_rows, int* targets, uint64_t* error, void* stream);
+int ottohip_submission_parse(ottohip_ctx* ctx, const uint8_t* text, int64_t n_bytes, int first, int64_t line_base,
+                             int64_t byte_base, int32_t* const* session, int32_t* const* aid_next,
+                             const int64_t* cap_rows, void* stream);
+
 /* Test hooks for the device primitives the engine is built from (parity tests only). */
 int ottohip_test_exclusive_scan_u32(ottohip_ctx* ctx, const uint32_t* in, uint64_t* out, int64_t n,
                                     uint64_t* total_host, void* stream);

@@ -261,6 +261,15 @@ SIGNATURES = {
                                            _VP]),
     "ottohip_jsonl_sessions": (ctypes.c_int, [_VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _I64, _VP]),
     "ottohip_jsonl_labels": (ctypes.c_int, [_VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _I64, _I64, _VP]),
+    "ottohip_submit_plan": (ctypes.c_int, [_VP, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP),
+                                           ctypes.POINTER(_I64), ctypes.c_int, ctypes.POINTER(_VP), ctypes.POINTER(_I64),
+                                           ctypes.POINTER(_I64), ctypes.POINTER(_I64), _VP]),
+    "ottohip_submit_write": (ctypes.c_int, [_VP, _VP, _VP, _I64, _VP]),
+    "ottohip_submit_free": (None, [_VP]),
+    "ottohip_submission_scan": (ctypes.c_int, [_VP, _VP, _I64, ctypes.c_int, ctypes.POINTER(_I64), ctypes.POINTER(_I64),
+                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64), _VP]),
+    "ottohip_submission_parse": (ctypes.c_int, [_VP, _VP, _I64, ctypes.c_int, _I64, _I64, ctypes.POINTER(_VP),
+                                                ctypes.POINTER(_VP), ctypes.POINTER(_I64), _VP]),
     "ottohip_test_exclusive_scan_u32": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.POINTER(ctypes.c_uint64), _VP]),
     "ottohip_test_radix_sort_pairs": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.c_int, _VP]),
     "ottohip_test_lanes": (ctypes.c_int, [_VP, _VP, _VP]),

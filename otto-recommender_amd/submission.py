@@ -7,6 +7,11 @@ joined row count of :48, clipped); a session with labels and nothing submitted a
 labels add nothing. recall@20 = sum hit / sum true per type. The sums are computed in libottohip.so
 (csrc/downsample.hip, ottohip_submission_recall) from two CSRs over the sorted union of session ids; ranked rows go
 in as they come out of the rank stage, device tensors or DataFrames, never through strings.
+
+The Kaggle csv itself (model/submit.py:32-60) is written and parsed on the device too (csrc/submit.hip):
+submission_bytes / write_submission / submit turn ranked rows into the file's bytes, read_submission turns a file
+back into rows under a strict grammar, eval_submission(device=True) scores a file that way. parse_submission and
+the default path of eval_submission are the host route and stay as they were.
 """
 from __future__ import annotations
 
@@ -119,18 +124,27 @@ def parse_submission(df) -> dict:
 
 
 def eval_submission(file_submit_or_frame, df_labels, dir_out: str | None = None, name: str | None = None,
-                    ctx=None) -> dict:
+                    ctx=None, device: bool = False) -> dict:
     """The __main__ of model/eval_submission.py: a submission csv (or its DataFrame[session_type, labels]) scored
     against df_labels [session, aid, type]. With dir_out also writes {dir_out}/{name}.json (the four figures, keys
     sorted) and {dir_out}/{name}.csv ([type, recall@20], rows clicks, carts, orders, total) (:67-70); name defaults
-    to the file's basename, or 'submission'."""
+    to the file's basename, or 'submission'. device=True (a path or the file's bytes): the file is parsed on the
+    device by read_submission, under its strict grammar, instead of pandas.read_csv and parse_submission."""
     import pandas as pd
-    if isinstance(file_submit_or_frame, (str, os.PathLike)):
-        df = pd.read_csv(file_submit_or_frame, dtype=str)
-        name = name or os.path.basename(str(file_submit_or_frame))
+    if device:
+        if isinstance(file_submit_or_frame, (str, os.PathLike)):
+            name = name or os.path.basename(str(file_submit_or_frame))
+        elif not isinstance(file_submit_or_frame, (bytes, bytearray, memoryview)):
+            raise TypeError("eval_submission(device=True) takes a path or the file's bytes")
+        ranked = read_submission(file_submit_or_frame, ctx=ctx)
     else:
-        df = file_submit_or_frame
-    res = eval_ranked(parse_submission(df), df_labels, ctx)
+        if isinstance(file_submit_or_frame, (str, os.PathLike)):
+            df = pd.read_csv(file_submit_or_frame, dtype=str)
+            name = name or os.path.basename(str(file_submit_or_frame))
+        else:
+            df = file_submit_or_frame
+        ranked = parse_submission(df)
+    res = eval_ranked(ranked, df_labels, ctx)
     if dir_out is not None:
         stem = (name or "submission")
         stem = stem[:-4] if stem.endswith(".csv") else stem
@@ -141,3 +155,233 @@ def eval_submission(file_submit_or_frame, df_labels, dir_out: str | None = None,
         pd.DataFrame({"type": order, "recall@20": [res[k] for k in order]}).to_csv(os.path.join(dir_out, stem + ".csv"),
                                                                                      index=False)
     return res
+
+
+# ---------------------------------------------------------------- the csv on the device (csrc/submit.hip)
+HEADER = b"session_type,labels\n"
+_ALPHA_RANK = {"carts": 0, "clicks": 1, "orders": 2}
+_NO_ERROR = (1 << 64) - 1
+
+
+def line_key(session, target: str):
+    """The integer (below 2^37) that orders the lines as their session_type strings order: the session's decimal
+    digits left-justified in a 10-place base-11 number whose empty places hold 10 ('_' sorts above every digit, so
+    "123_carts" < "12_carts"), times 3, plus the target's alphabetical rank. numpy, int64; sessions in [0, 2^31)."""
+    s = np.asarray(session, dtype=np.int64)
+    if s.size and (s.min() < 0 or s.max() > 2147483647):
+        raise ValueError("line_key: sessions lie in [0, 2^31)")
+    d = np.ones(s.shape, np.int64)
+    for k in range(1, 10):
+        d += s >= 10 ** k
+    pw = 11 ** (10 - d)
+    acc = pw - 1  # the empty places
+    v = s.copy()
+    for i in range(10):
+        live = i < d
+        acc = acc + np.where(live, (v % 10) * pw, 0)
+        v //= 10
+        pw = np.where(live, pw * 11, pw)
+    return acc * 3 + _ALPHA_RANK[target]
+
+
+def _triple(r, dev):
+    """(session int32, aid_next int32, pred_rank int16) of one target on the device, from what _pair takes"""
+    import torch
+    def get(c, dt):
+        v = r[c]
+        if not isinstance(v, torch.Tensor):
+            v = torch.from_numpy(np.ascontiguousarray(v.to_numpy() if hasattr(v, "to_numpy") else v))
+        return v.to(dev, dt).contiguous()
+    return get("session", torch.int32), get("aid_next", torch.int32), get("pred_rank", torch.int16)
+
+
+def _submit_plan(ranked: dict, keep_top_k: int, ctx=None, stream=None):
+    """ottohip_submit_plan -> (context, plan handle, data lines, bytes of the file); the plan holds its own copy of
+    the kept rows, so the columns may go once it returns"""
+    import torch
+    k = int(keep_top_k)
+    if not 1 <= k <= 64:
+        raise ValueError(f"keep_top_k={keep_top_k} outside [1, 64]")
+    _lib.require_gpu()
+    lib = _lib.load()
+    ctx = ctx or _lib.context()
+    dev = torch.device("cuda", ctx.device)
+    cols = {t: _triple(ranked[name], dev) for t, name in enumerate(config.TYPES) if name in ranked}
+    VP3 = ctypes.c_void_p * 3
+    arr = [VP3(*[_lib.ptr(cols[t][c]) if t in cols and cols[t][c].numel() else None for t in range(3)]) for c in range(3)]
+    n = (ctypes.c_int64 * 3)(*[int(cols[t][0].numel()) if t in cols else 0 for t in range(3)])
+    plan = ctypes.c_void_p()
+    n_lines, n_bytes, bad = ctypes.c_int64(0), ctypes.c_int64(0), (ctypes.c_int64 * 3)()
+    s = _lib.stream_handle(stream)
+    rc = lib.ottohip_submit_plan(ctx.h, arr[0], arr[1], arr[2], n, k, ctypes.byref(plan), ctypes.byref(n_lines),
+                                 ctypes.byref(n_bytes), bad, s)
+    if rc != 0 and any(bad):
+        raise ValueError(f"{sum(bad)} rows cannot be written: {bad[0]} with session < 0, {bad[1]} with aid_next < 0, "
+                         f"{bad[2]} with pred_rank < 1")
+    _lib.check(rc)
+    return ctx, plan, int(n_lines.value), int(n_bytes.value)
+
+
+def _submission_bytes(ranked: dict, keep_top_k: int, ctx=None, stream=None):
+    import torch
+    ctx, plan, n_lines, n_bytes = _submit_plan(ranked, keep_top_k, ctx, stream)
+    lib = _lib.load()
+    try:
+        out = torch.empty(n_bytes, dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+        _lib.check(lib.ottohip_submit_write(ctx.h, plan, _lib.ptr(out), n_bytes, _lib.stream_handle(stream)))
+    finally:
+        lib.ottohip_submit_free(plan)
+    return out, n_lines
+
+
+def submission_bytes(ranked: dict, keep_top_k: int = config.KEEP_TOP_K, ctx=None, stream=None):
+    """model/submit.py:36-60 on the device: the bytes of the submission csv as a uint8 device tensor, exactly what
+    rank.submission_frame(...).to_csv(index=False) writes for the rows with 1 <= pred_rank <= keep_top_k. ranked:
+    {target: {session, aid_next, pred_rank, ...}}, device tensors (Ranker.rank) or DataFrames (rank_job), rows in any
+    order; a target may be absent or empty. Lines are ordered by session_type as strings (line_key), a line's aids
+    by pred_rank, equal ranks in input order. pred_rank is taken from the column: on this project's ranked files it
+    equals what submit.py:38 recomputes, since the rows are each session's top-k in (session, pred_rank) order and
+    polars' ordinal rank breaks score ties by row order. Raises ValueError for keep_top_k outside [1, 64] (the rank
+    stage's bound) and for rows with session < 0, aid_next < 0 or pred_rank < 1, which are counted, not coerced."""
+    return _submission_bytes(ranked, keep_top_k, ctx, stream)[0]
+
+
+def write_submission(ranked: dict, file_out, keep_top_k: int = config.KEEP_TOP_K, ctx=None) -> int:
+    """submission_bytes to a file: one copy to the host, through pinned memory. Returns the number of data lines."""
+    import torch
+    buf, n_lines = _submission_bytes(ranked, keep_top_k, ctx)
+    pin = torch.empty(buf.numel(), dtype=torch.uint8, pin_memory=True)
+    pin.copy_(buf)
+    os.makedirs(os.path.dirname(os.path.abspath(file_out)), exist_ok=True)
+    with open(file_out, "wb") as fh:
+        fh.write(memoryview(pin.numpy()))
+    return n_lines
+
+
+def _grammar_error(e):
+    """The ValueError of a submission_parse verdict (line, offset and reason as attributes), or None"""
+    import re
+    m = re.search(r"submission_parse: line (\d+), byte (\d+): (.*)$", str(e))
+    if not m:
+        return None
+    err = ValueError(f"submission csv: line {m.group(1)}, byte {m.group(2)}: {m.group(3)}")
+    err.line, err.offset, err.reason = int(m.group(1)), int(m.group(2)), m.group(3)
+    return err
+
+
+def _scan_piece(ctx, text, n: int, first: bool):
+    """ottohip_submission_scan -> (data lines, rows per target, mask of the targets seen, the error word)"""
+    n_lines, rows, seen = ctypes.c_int64(0), (ctypes.c_int64 * 3)(), ctypes.c_int(0)
+    word = ctypes.c_uint64(0)
+    _lib.check(_lib.load().ottohip_submission_scan(ctx.h, _lib.ptr(text), n, int(first), ctypes.byref(n_lines), rows,
+                                                   ctypes.byref(seen), ctypes.byref(word), _lib.stream_handle()))
+    return int(n_lines.value), list(rows), int(seen.value), int(word.value)
+
+
+def _read_piece(ctx, text, n: int, first: bool, line_base: int, byte_base: int):
+    """One resident piece -> ([(session, aid_next)] per target, mask of the targets seen, data lines)"""
+    import torch
+    lib = _lib.load()
+    s = _lib.stream_handle()
+    n_lines, rows, seen, word = _scan_piece(ctx, text, n, first)
+    ok = word == _NO_ERROR
+    dev = text.device
+    cols = [(torch.empty(rows[t] if ok else 0, dtype=torch.int32, device=dev),
+             torch.empty(rows[t] if ok else 0, dtype=torch.int32, device=dev)) for t in range(3)]
+    VP3 = ctypes.c_void_p * 3
+    ses = VP3(*[_lib.ptr(c[0]) if c[0].numel() else None for c in cols])
+    aid = VP3(*[_lib.ptr(c[1]) if c[1].numel() else None for c in cols])
+    cap = (ctypes.c_int64 * 3)(*[c[0].numel() for c in cols])
+    try:  # a bad line head: the parse only validates, and names the first bad byte of the piece
+        _lib.check(lib.ottohip_submission_parse(ctx.h, _lib.ptr(text), n, int(first), line_base, byte_base,
+                                                ses if ok else None, aid if ok else None, cap if ok else None, s))
+    except _lib.OttoHipError as e:
+        err = _grammar_error(e)
+        if err is None:
+            raise
+        raise err from None
+    if not ok:
+        raise ValueError("submission csv: a line head outside the grammar")
+    return cols, seen, n_lines
+
+
+def read_submission(path_or_bytes, piece_bytes: int | None = None, ctx=None) -> dict:
+    """A submission csv (a path, the file's bytes, or a uint8 device tensor holding them) -> {target: {"session":
+    int32, "aid_next": int32}} on the device, one row per submitted aid in file order, ready for eval_ranked: what
+    parse_submission(pd.read_csv(path, dtype=str)) returns for the same file. A target is present when a line names
+    it, also when all its lines have empty labels (zero rows). The file is read in pieces of whole lines through
+    the ETL's pinned double buffer. The grammar is strict (Submission csv), stricter than int() and
+    pd.read_csv on purpose, as the ETL is stricter than pandas: quotes, '\\r', tabs, doubled or trailing spaces, signs,
+    leading zeros, an unknown target, a missing comma, a wrong or missing header and numbers above int32 raise
+    ValueError naming the line and the byte offset of the first offending byte (attributes line, offset, reason)."""
+    import io
+    import torch
+    from . import etl
+    _lib.require_gpu()
+    ctx = ctx or _lib.context()
+    dev = torch.device("cuda", ctx.device)
+    parts, seen = [[], [], []], 0
+
+    def take(text, n, first, line_base, byte_base):
+        nonlocal seen
+        cols, mask, n_lines = _read_piece(ctx, text, n, first, line_base, byte_base)
+        for t in range(3):
+            parts[t].append(cols[t])
+        seen |= mask
+        return n_lines + (1 if first else 0)
+
+    if isinstance(path_or_bytes, torch.Tensor):
+        text = path_or_bytes.to(dev, torch.uint8).contiguous()
+        if text.data_ptr() & 15:
+            text = text.clone()
+        if text.numel() == 0:
+            raise _grammar_error("submission_parse: line 1, byte 0: text ends inside the line")
+        take(text, text.numel(), True, 0, 0)
+    else:
+        fp = open(path_or_bytes, "rb") if isinstance(path_or_bytes, (str, os.PathLike)) else io.BytesIO(path_or_bytes)
+        up = etl._Uploader(dev)
+        try:
+            it = etl._pieces(fp, piece_bytes or etl.PIECE_BYTES)
+            nxt = next(it, None)
+            if nxt is None:
+                raise _grammar_error("submission_parse: line 1, byte 0: text ends inside the line")
+            cur = up.put(nxt)
+            first, line_base, byte_base = True, 0, 0
+            while cur is not None:
+                nxt = next(it, None)
+                ahead = up.put(nxt) if nxt is not None else None  # uploads while this piece is parsed
+                text, n, ev = cur
+                torch.cuda.current_stream(dev).wait_event(ev)
+                line_base += take(text, n, first, line_base, byte_base)
+                byte_base += n
+                first, cur = False, ahead
+        finally:
+            up.stream.synchronize()  # no copy is in flight when the buffers go back to the allocator
+            fp.close()
+    out = {}
+    for t, name in enumerate(config.TYPES):
+        if seen >> t & 1:
+            out[name] = {"session": parts[t][0][0] if len(parts[t]) == 1 else torch.cat([p[0] for p in parts[t]]),
+                         "aid_next": parts[t][0][1] if len(parts[t]) == 1 else torch.cat([p[1] for p in parts[t]])}
+    return out
+
+
+def submit(dir_ranked: str, dir_out: str, keep_top_k: int = 20, tag: str | None = None, name: str | None = None,
+           ctx=None) -> str:
+    """The __main__ of model/submit.py: {dir_ranked}/{target}/*.parquet (the files rank_files writes, taken in the
+    order of their names; a target without a folder is absent) -> {dir_out}/{name}.csv; returns the path. name
+    defaults to 'submission', or 'submission-{tag}' with a tag. The reference also puts a timestamp and the commit
+    hash into the name (utils.py:70-74); they are left out here so that a rerun overwrites its file."""
+    import glob
+    import pyarrow.parquet as pq
+    ranked = {}
+    for target in config.TYPES:
+        files = sorted(glob.glob(os.path.join(dir_ranked, target, "*.parquet")))
+        if not files:
+            continue
+        tabs = [pq.read_table(f, columns=["session", "aid_next", "pred_rank"]) for f in files]
+        ranked[target] = {c: np.concatenate([t[c].to_numpy() for t in tabs]) for c in ("session", "aid_next", "pred_rank")}
+    name = name or ("submission" if tag is None else f"submission-{tag}")
+    path = os.path.join(dir_out, f"{name}.csv")
+    write_submission(ranked, path, keep_top_k, ctx)
+    return path
