@@ -891,6 +891,29 @@ int ottohip_test_radix_sort_pairs(ottohip_ctx* ctx, uint32_t* keys, uint32_t* va
 /* cross-lane moves of one wave on in[64] (device): out[k*64 + l] for k = 0..5 the value of lane
  * l ^ (1 << k); k = 6, 7: inclusive sum / max scan; k = 8, 9: lanes l-1 / l+1 (0 off the ends) */
 int ottohip_test_lanes(const uint32_t* in, uint32_t* out, void* stream);
+/* The rest of csrc/prims.h, called as the engine calls it.
+ * exclusive_scan_u32 / _u64 (width = 32 / 64; out may alias in for 64): want_total != 0 passes a device total and
+ * returns it in *total_host, 0 passes nullptr and leaves *total_host alone. */
+int ottohip_test_scan(ottohip_ctx* ctx, const void* in, uint64_t* out, int64_t n, int width, int want_total,
+                      uint64_t* total_host, void* stream);
+/* radix_sort_pairs with every option (use_skip: SortSkip{skip_mask, skip_inv}); the result is copied back into
+ * keys / vals, with skip its first *n_out entries (*n_out = n without skip). The sort's error codes pass through. */
+int ottohip_test_sort_pairs(ottohip_ctx* ctx, uint32_t* keys, uint32_t* vals, int64_t n, int bits, int shift0,
+                            int iota_vals, int use_skip, uint32_t skip_mask, uint32_t skip_inv, int64_t* n_out,
+                            void* stream);
+/* radix_pass at `shift` / radix_skip_pass into the caller's buffers. *n_tiles = the pass's tile count and
+ * digit_start (device, digit_start_cap >= 256 * *n_tiles u64, may be NULL) = a copy of its offset matrix,
+ * [d * *n_tiles + t]. */
+int ottohip_test_radix_pass(ottohip_ctx* ctx, const uint32_t* kin, const uint32_t* vin, uint32_t* kout,
+                            uint32_t* vout, int64_t n, int shift, uint64_t* digit_start, int64_t digit_start_cap,
+                            int* n_tiles, void* stream);
+int ottohip_test_radix_skip_pass(ottohip_ctx* ctx, const uint32_t* keys, uint32_t* kout, uint32_t* vout, int64_t n,
+                                 uint32_t skip_mask, uint32_t skip_inv, int64_t* n_out, uint64_t* digit_start,
+                                 int64_t digit_start_cap, int* n_tiles, void* stream);
+/* lds_add_runs by one wave: lane l adds digits[l] (device, 64) when l < nv, onto the histogram hist_in (device, 256);
+ * rank_out[64] = each lane's returned rank, hist_out[256] = the histogram afterwards. */
+int ottohip_test_lds_add_runs(const uint32_t* digits, int nv, const uint32_t* hist_in, uint32_t* rank_out,
+                              uint32_t* hist_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -273,6 +273,17 @@ SIGNATURES = {
     "ottohip_test_exclusive_scan_u32": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.POINTER(ctypes.c_uint64), _VP]),
     "ottohip_test_radix_sort_pairs": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.c_int, _VP]),
     "ottohip_test_lanes": (ctypes.c_int, [_VP, _VP, _VP]),
+    "ottohip_test_scan": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.c_int, ctypes.c_int,
+                                         ctypes.POINTER(ctypes.c_uint64), _VP]),
+    "ottohip_test_sort_pairs": (ctypes.c_int, [_VP, _VP, _VP, _I64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_I64),
+                                               _VP]),
+    "ottohip_test_radix_pass": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _I64, ctypes.c_int, _VP, _I64,
+                                               ctypes.POINTER(ctypes.c_int), _VP]),
+    "ottohip_test_radix_skip_pass": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I64, ctypes.c_uint32, ctypes.c_uint32,
+                                                    ctypes.POINTER(_I64), _VP, _I64, ctypes.POINTER(ctypes.c_int),
+                                                    _VP]),
+    "ottohip_test_lds_add_runs": (ctypes.c_int, [_VP, ctypes.c_int, _VP, _VP, _VP, _VP]),
 }
 
 _LIB = None

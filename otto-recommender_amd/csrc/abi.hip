@@ -1407,6 +1407,101 @@ int ottohip_test_radix_sort_pairs(ottohip_ctx* ctx, uint32_t* keys, uint32_t* va
   return 0;
 }
 
+int ottohip_test_scan(ottohip_ctx* ctx, const void* in, uint64_t* out, int64_t n, int width, int want_total,
+                      uint64_t* total_host, void* stream) {
+  if (!ctx || n < 0 || (width != 32 && width != 64) || (want_total && !total_host)) return OTTOHIP_EINVAL;
+  uint64_t* tot = nullptr;
+  if (want_total) {  // poisoned, so a scan that leaves the total alone shows
+    OH_TRY(ctx->ws.get("test_total", 1, &tot));
+    OH_HIP(hipMemsetAsync(tot, 0xA5, sizeof(uint64_t), S(stream)));
+  }
+  if (width == 32) OH_TRY(exclusive_scan_u32(ctx, static_cast<const uint32_t*>(in), out, n, tot, S(stream)));
+  else OH_TRY(exclusive_scan_u64(ctx, static_cast<const uint64_t*>(in), out, n, tot, S(stream)));
+  if (want_total) OH_TRY(d2h(total_host, tot, 1, S(stream)));
+  return 0;
+}
+
+int ottohip_test_sort_pairs(ottohip_ctx* ctx, uint32_t* keys, uint32_t* vals, int64_t n, int bits, int shift0,
+                            int iota_vals, int use_skip, uint32_t skip_mask, uint32_t skip_inv, int64_t* n_out,
+                            void* stream) {
+  if (!ctx || !n_out || n < 0 || bits < 0 || bits > 32 || shift0 < 0 || shift0 > 24 || (shift0 & 7))
+    return OTTOHIP_EINVAL;
+  uint32_t *ka, *va;
+  OH_TRY(ctx->ws.get("test_ka", (size_t)std::max<int64_t>(n, 1), &ka));
+  OH_TRY(ctx->ws.get("test_va", (size_t)std::max<int64_t>(n, 1), &va));
+  uint32_t *k = keys, *v = vals;
+  int64_t kept = n;
+  const SortSkip skip{skip_mask, skip_inv, &kept};
+  const int rc = radix_sort_pairs(ctx, k, v, ka, va, n, bits, S(stream), iota_vals != 0, use_skip ? &skip : nullptr,
+                                  shift0);
+  *n_out = kept;
+  if (rc) return rc;
+  if (k != keys && kept > 0) {
+    OH_HIP(hipMemcpyAsync(keys, k, kept * sizeof(uint32_t), hipMemcpyDeviceToDevice, S(stream)));
+    OH_HIP(hipMemcpyAsync(vals, v, kept * sizeof(uint32_t), hipMemcpyDeviceToDevice, S(stream)));
+  }
+  return 0;
+}
+
+// the pass's digit_start matrix lives in the context's workspace until the next pass: copied out here
+static int test_copy_digit_start(const uint64_t* ds, int nt, uint64_t* digit_start, int64_t digit_start_cap,
+                                 int* n_tiles, hipStream_t s) {
+  if (n_tiles) *n_tiles = nt;
+  if (!digit_start || !ds || nt <= 0) return 0;
+  if (digit_start_cap < (int64_t)256 * nt) { set_error("test hook: digit_start_cap too small"); return OTTOHIP_EINVAL; }
+  OH_HIP(hipMemcpyAsync(digit_start, ds, (size_t)256 * nt * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+int ottohip_test_radix_pass(ottohip_ctx* ctx, const uint32_t* kin, const uint32_t* vin, uint32_t* kout,
+                            uint32_t* vout, int64_t n, int shift, uint64_t* digit_start, int64_t digit_start_cap,
+                            int* n_tiles, void* stream) {
+  if (!ctx || n < 0 || shift < 0 || shift > 24 ||
+      (digit_start && digit_start_cap < 256 * ceil_div(n, RADIX_TILE_KEYS)))
+    return OTTOHIP_EINVAL;
+  const uint64_t* ds = nullptr;
+  int nt = 0;
+  OH_TRY(radix_pass(ctx, kin, vin, kout, vout, n, shift, S(stream), &ds, &nt));
+  return test_copy_digit_start(ds, nt, digit_start, digit_start_cap, n_tiles, S(stream));
+}
+
+int ottohip_test_radix_skip_pass(ottohip_ctx* ctx, const uint32_t* keys, uint32_t* kout, uint32_t* vout, int64_t n,
+                                 uint32_t skip_mask, uint32_t skip_inv, int64_t* n_out, uint64_t* digit_start,
+                                 int64_t digit_start_cap, int* n_tiles, void* stream) {
+  if (!ctx || !n_out || n < 0 || (digit_start && digit_start_cap < 256 * ceil_div(n, RADIX_TILE_KEYS)))
+    return OTTOHIP_EINVAL;
+  const uint64_t* ds = nullptr;
+  int nt = 0;
+  int64_t kept = 0;
+  const SortSkip skip{skip_mask, skip_inv, &kept};
+  const int rc = radix_skip_pass(ctx, keys, kout, vout, n, S(stream), skip, &ds, &nt);
+  *n_out = kept;
+  if (rc) return rc;
+  return test_copy_digit_start(ds, nt, digit_start, digit_start_cap, n_tiles, S(stream));
+}
+
+__global__ __launch_bounds__(64) void k_test_lds_add_runs(const uint32_t* __restrict__ digits, int nv,
+                                                          const uint32_t* __restrict__ hist_in,
+                                                          uint32_t* __restrict__ rank_out,
+                                                          uint32_t* __restrict__ hist_out) {
+  __shared__ uint32_t h[256];
+  const uint32_t l = lane_id();
+  for (int i = l; i < 256; i += 64) h[i] = hist_in[i];
+  __syncthreads();
+  const uint32_t r = lds_add_runs(h, digits[l] & 255u, (int)l < nv);
+  __syncthreads();
+  rank_out[l] = r;
+  for (int i = l; i < 256; i += 64) hist_out[i] = h[i];
+}
+
+int ottohip_test_lds_add_runs(const uint32_t* digits, int nv, const uint32_t* hist_in, uint32_t* rank_out,
+                              uint32_t* hist_out, void* stream) {
+  if (!digits || !hist_in || !rank_out || !hist_out || nv < 0 || nv > 64) return OTTOHIP_EINVAL;
+  k_test_lds_add_runs<<<1, 64, 0, S(stream)>>>(digits, nv, hist_in, rank_out, hist_out);
+  OH_HIP(hipGetLastError());
+  return 0;
+}
+
 static void file_opts_zero(const ottohip_file_opts* o) {
   if (!o) return;
   for (int f = 0; f < o->n_files; ++f) {

@@ -7,17 +7,23 @@ int exclusive_scan_u32(Ctx* ctx, const uint32_t* in, uint64_t* out, int64_t n, u
                        hipStream_t s);
 int exclusive_scan_u64(Ctx* ctx, const uint64_t* in, uint64_t* out, int64_t n, uint64_t* total,
                        hipStream_t s);
-// stable LSD sort of (key, val) by key bits [0, bits); ping-pongs with the *_alt buffers and
-// returns the buffers holding the result in keys/vals
+// stable LSD sort of (key, val) in whole 8-bit passes from bit shift0 up to bits, rounded up to a byte: the result
+// is the stable order by key bits [shift0, 8 * ceil(bits / 8)); key bits at or above that are carried unchanged and
+// do not order anything (the co-visitation rows carry a count above a byte-aligned key). Ping-pongs with the *_alt
+// buffers and returns the buffers holding the result in keys/vals
 // iota_vals: the input values are their own indices (0..n-1); the first pass generates them
 // instead of reading vals (vals still provides the buffer)
 // skip (with iota_vals): the first pass drops keys with (key & mask) == inv and the later passes sort the
-// *n_out kept pairs (the first pass' total, read back on the host)
+// *n_out kept pairs (the first pass' total, read back on the host).
+// inv must lie inside mask, (inv & ~mask) == 0: the passes pad their last tile with inv and rely on the padding
+// being dropped. radix_skip_pass, and radix_sort_pairs with skip, return OTTOHIP_EINVAL for any other pair and
+// launch nothing
 struct SortSkip {
   uint32_t mask, inv;
   int64_t* n_out;
 };
-// shift0 (a multiple of 8, without skip): the passes start at this bit, for pairs already ordered by the bits below it
+// shift0 (a multiple of 8, without skip): the passes start at this bit; the input must already be ordered by the
+// key bits [0, shift0), and the result is then ordered by the bits [0, 8 * ceil(bits / 8))
 int radix_sort_pairs(Ctx* ctx, uint32_t*& keys, uint32_t*& vals, uint32_t* keys_alt, uint32_t* vals_alt,
                      int64_t n, int bits, hipStream_t s, bool iota_vals = false, const SortSkip* skip = nullptr,
                      int shift0 = 0);

@@ -262,6 +262,10 @@ int radix_pass(Ctx* ctx, const uint32_t* kin, const uint32_t* vin, uint32_t* kou
 int radix_skip_pass(Ctx* ctx, const uint32_t* keys, uint32_t* kout, uint32_t* vout, int64_t n, hipStream_t s,
                     const SortSkip& skip, const uint64_t** digit_start, int* n_tiles) {
   *skip.n_out = 0;
+  if (skip.inv & ~skip.mask) {  // the padding of the last tile (= inv) would be counted and not written (prims.h)
+    set_error("radix_skip_pass: inv=0x%x has bits outside mask=0x%x", skip.inv, skip.mask);
+    return OTTOHIP_EINVAL;
+  }
   if (n <= 0) return 0;
   if (n >= ((int64_t)1 << 32)) { set_error("radix_skip_pass: n=%lld too large", (long long)n); return OTTOHIP_ELIMIT; }
   const int nb = (int)ceil_div(n, RS_BLOCK);
@@ -291,6 +295,10 @@ int radix_sort_pairs(Ctx* ctx, uint32_t*& keys, uint32_t*& vals, uint32_t* keys_
       return OTTOHIP_EINVAL;
     }
     *skip->n_out = 0;
+    if (skip->inv & ~skip->mask) {
+      set_error("radix_sort_pairs: skip inv=0x%x has bits outside mask=0x%x", skip->inv, skip->mask);
+      return OTTOHIP_EINVAL;
+    }
     if (n <= 0) return 0;
     OH_TRY(radix_skip_pass(ctx, keys, keys_alt, vals_alt, n, s, *skip));
     std::swap(keys, keys_alt); std::swap(vals, vals_alt);
