@@ -307,16 +307,6 @@ static PrepPlan prep_plan(const RulesDev& R) {
   return P;
 }
 
-static ottohip_table* new_table(ottohip_ctx* ctx, int n_rules, int32_t n_items) {
-  ottohip_table* T = new ottohip_table();
-  T->device = ctx->device;
-  T->n_rules = n_rules;
-  T->n_items = n_items;
-  T->ctx = ctx;
-  memset(T->stats, 0, sizeof T->stats);
-  return T;
-}
-
 // The multi-GPU row keys' owner map for (n_items, G), in the context workspace: a2l[aid] = the aid's index among
 // the aids of its owner (aid order), l2a[obase[o] + i] = the inverse; *LB = bits of the largest owner's count.
 static int owner_map(ottohip_ctx* ctx, int32_t n_items, int G, hipStream_t s, const uint32_t** a2l,
@@ -764,28 +754,524 @@ static int file_opts_finish(const ottohip_file_opts* o, const FileOpts& fo, hipS
   return 0;
 }
 
+static int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+
+// S5's plan of one reduce call: every environment switch and every derived condition of the driver. "process": read
+// once per process (the statics of reduce_plan); "call": read at every call (the tests toggle these in-process).
+struct ReducePlan {
+  // process
+  bool overlap;     // OTTOHIP_REDUCE_OVERLAP=0: everything on the caller's stream (s2 stays null)
+  int rdbg;         // OTTOHIP_REDUCE_DBG (profiling ablation): bit 0 drops the register sorts' row stores
+  int split_mean, hash_prio, sub;  // OTTOHIP_SPLIT_MEAN, OTTOHIP_HASH_PRIO, OTTOHIP_SPLIT_SUB (A/B switches)
+  bool split_runs, split_unfused;  // OTTOHIP_SPLIT_RUNS=1, OTTOHIP_SPLIT_FUSE=0 (A/B switches)
+  bool hash_first;  // the level's LDS-hash leaves are queued before its register sorts, so their few long-running blocks
+                    // take CU slots before the sorts' many short ones (step -0.5 ms same box; OTTOHIP_HASH_FIRST=0: after)
+  bool hprof;       // OTTOHIP_HASH_PROF set and sorts first: the per-task hash profile (debugging aid)
+  // call
+  bool rdbg_fill;      // OTTOHIP_REDUCE_DBG set: the slots are filled with rule 0xFF first
+  bool hash_prof_set;  // OTTOHIP_HASH_PROF set
+  bool lds_leaf;       // OTTOHIP_LDS_LEAF=1: the LDS leaf (k_agg_lds) for rows and split buckets of (SORT_MAX, LDS_CAP] words,
+                       // fed by splits of LDS_SPLIT_MEAN-word buckets (default: register sorts of SPLIT_MEAN-word buckets)
+  bool dbg, pipe_log;  // OTTOHIP_DEBUG: the level listings; OTTOHIP_SPLIT_PIPE_LOG: one line per pipelined split
+  bool pipe_on;        // OTTOHIP_SPLIT_PIPE=1
+  uint64_t PIPE_MIN_CHUNKS;  // splits of >= 2048 chunks (32 M words) are pipelined (OTTOHIP_SPLIT_PIPE_MIN: for tests)
+  // OTTOHIP_HASH_GRID, the hash leaf grid (hash_blocks). Unset (-1): as many blocks as are resident at once (two per CU),
+  // which take their tasks from a device counter; n > 0: n blocks, the same; 0: n_cu * 8 blocks striding over the tasks
+  int hgrid; int64_t hash_blocks;
+  // OTTOHIP_SPLIT_LDS (0: off): chunks of >= lds_min words (OTTOHIP_SPLIT_LDS_MIN) are scattered by k_split_scatter_lds
+  // (lds_t threads: OTTOHIP_SPLIT_LDS_T, A/B switch), a whole chunk staged in LDS; the shorter ones by k_split_scatter
+  // as before. Both kernels run over the same chunks and each leaves the other's at once.
+  bool split_lds; uint32_t lds_min; int lds_t;
+  // derived. FOon: file options; fom, the FOM template argument of the leaves: 0 none; 1 key cuts or part mode; 2
+  // per-file rows only (the register sorts keep their occupancy); 3 part mode with explicit mirror rows
+  bool FOon; int fom;
+  hipStream_t s2;  // the aux stream (overlap)
+  // reduce_levels_sched (OTTOHIP_REDUCE_SCHED=1, call) instead of reduce_levels_blocking. Built and measured, off by
+  // default: the split then shares the CUs with the level's register sorts and ends when it did before. The
+  // split pipelining, the LDS leaf and the per-task hash profile are written against the other loop and select it.
+  bool sched;
+  bool pipe;  // split_second_half (off by default: step 57.0-57.3 vs 57.0-57.1 ms same box, the early leaves and the
+              // second half's scatter contend for the same CUs)
+};
+
+// FOM (0..3) as a template argument: f(std::integral_constant<int, FOM>)
+template <class F>
+static void with_fom(int fom, F&& f) {
+  if (fom == 1) f(std::integral_constant<int, 1>());
+  else if (fom == 2) f(std::integral_constant<int, 2>());
+  else if (fom == 3) f(std::integral_constant<int, 3>());
+  else f(std::integral_constant<int, 0>());
+}
+
+static int reduce_plan(ottohip_ctx* ctx, const FileOpts& fo, bool FOon, ReducePlan& P) {
+  static const ReducePlan process = [] {
+    ReducePlan Q{};
+    Q.overlap = !env_is("OTTOHIP_REDUCE_OVERLAP", "0"); Q.rdbg = env_int("OTTOHIP_REDUCE_DBG", 0);
+    Q.split_mean = env_int("OTTOHIP_SPLIT_MEAN", SPLIT_MEAN); Q.hash_prio = env_int("OTTOHIP_HASH_PRIO", 0);
+    Q.sub = env_int("OTTOHIP_SPLIT_SUB", 4096);
+    Q.split_runs = env_is("OTTOHIP_SPLIT_RUNS", "1"); Q.split_unfused = env_is("OTTOHIP_SPLIT_FUSE", "0");
+    Q.hash_first = !env_is("OTTOHIP_HASH_FIRST", "0"); Q.hprof = getenv("OTTOHIP_HASH_PROF") != nullptr && !Q.hash_first;
+    return Q;
+  }();
+  P = process;
+  P.rdbg_fill = getenv("OTTOHIP_REDUCE_DBG") != nullptr; P.hash_prof_set = getenv("OTTOHIP_HASH_PROF") != nullptr;
+  P.lds_leaf = env_is("OTTOHIP_LDS_LEAF", "1"); P.pipe_on = env_int("OTTOHIP_SPLIT_PIPE", 0) == 1;
+  P.dbg = getenv("OTTOHIP_DEBUG") != nullptr; P.pipe_log = getenv("OTTOHIP_SPLIT_PIPE_LOG") != nullptr;
+  P.PIPE_MIN_CHUNKS = getenv("OTTOHIP_SPLIT_PIPE_MIN") ? (uint64_t)atoll(getenv("OTTOHIP_SPLIT_PIPE_MIN")) : 2048;
+  P.hgrid = getenv("OTTOHIP_HASH_GRID") ? std::max(0, atoi(getenv("OTTOHIP_HASH_GRID"))) : -1;
+  P.split_lds = getenv("OTTOHIP_SPLIT_LDS") ? atoi(getenv("OTTOHIP_SPLIT_LDS")) != 0 : SPLIT_LDS_DEFAULT;
+  P.lds_min = (uint32_t)std::min(SPLIT_CH + 1, std::max(0, env_int("OTTOHIP_SPLIT_LDS_MIN", SPLIT_LDS_MIN)));
+  P.lds_t = env_int("OTTOHIP_SPLIT_LDS_T", SPLIT_LT);
+  P.FOon = FOon;
+  const bool FOhist = FOon && !fo.cuts && !fo.parts && fo.hist != nullptr, FOmir = FOon && fo.parts && fo.mirror_off != 0;
+  P.fom = FOhist ? 2 : (FOmir ? 3 : (FOon ? 1 : 0));
+  if (P.overlap) { OH_TRY(ctx->aux_stream()); P.s2 = ctx->aux; }
+  P.sched = P.s2 != nullptr && env_int("OTTOHIP_REDUCE_SCHED", 0) == 1 && !P.pipe_on && !P.lds_leaf && !P.hash_prof_set;
+  P.pipe = P.s2 != nullptr && !P.lds_leaf && !P.dbg && !P.hash_prof_set && P.pipe_on;
+  if (P.hgrid < 0 && !ctx->hash_resident[P.fom]) {  // queried once per template instance and context
+    int nb = 0;
+    hipError_t e = hipErrorUnknown;
+    with_fom(P.fom, [&](auto M) { e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_agg_hash<decltype(M)::value>, AGG_T, 0); });
+    if (e != hipSuccess || nb < 1) { set_error("k_agg_hash<%d>: occupancy query failed", P.fom); return OTTOHIP_EHIP; }
+    ctx->hash_resident[P.fom] = nb * ctx->n_cu;
+  }
+  P.hash_blocks = P.hgrid == 0 ? ctx->n_cu * 8 : (P.hgrid > 0 ? P.hgrid : ctx->hash_resident[P.fom]);
+  return 0;
+}
+// the plan's switches that live in device constants (each device's code object has its own)
+static int reduce_constants(ottohip_ctx* ctx, const ReducePlan& P, hipStream_t s) {
+  auto upload = [s](const uint32_t& sym, uint32_t v, bool sync = true) -> int {
+    OH_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(sym), &v, sizeof v, 0, hipMemcpyHostToDevice, s));
+    if (sync) OH_HIP(hipStreamSynchronize(s));
+    return 0;
+  };
+  if (P.split_mean != SPLIT_MEAN) OH_TRY(upload(c_split_mean, (uint32_t)std::max(64, P.split_mean)));
+  if (P.split_runs) OH_TRY(upload(c_split_runs, 1u));
+  if (P.split_unfused) OH_TRY(upload(c_split_fuse, 0u));
+  static int8_t lds_state[64] = {};  // per device: 0 unset, 1 off, 2 on
+  int8_t& st = lds_state[ctx->device & 63];
+  if (st != (P.lds_leaf ? 2 : 1)) {
+    OH_TRY(upload(c_lds_leaf, P.lds_leaf ? 1u : 0u, P.split_mean != SPLIT_MEAN));
+    if (P.split_mean == SPLIT_MEAN) OH_TRY(upload(c_split_mean, P.lds_leaf ? (uint32_t)LDS_SPLIT_MEAN : (uint32_t)SPLIT_MEAN));
+    st = P.lds_leaf ? 2 : 1;
+  }
+  if (P.hash_prio) OH_TRY(upload(c_hash_prio, (uint32_t)P.hash_prio));
+  return 0;
+}
+
+// what the level steps of one reduce call share
+struct ReduceRun {
+  ottohip_ctx* ctx;
+  const ReducePlan* plan;
+  hipStream_t s, s2;        // the caller's stream; the aux stream (null: no overlap)
+  uint32_t *w0, *w1, *w2, *wcur0;  // wcur0: the word buffer of tasks with buf 0 at this level (w2 from level 1 on, if given)
+  const uint32_t* row_key;  // and the other arguments of the leaves
+  const RulesDev* R;
+  const Layout* Lt;
+  int n_rules;
+  OutRows O, Osort;  // Osort: the register sorts' (rdbg & 1: without their stores)
+  FileOpts fo;
+  TaskLists TL;  // double-buffered by level parity: level l's sorts (aux stream) may still read theirs while level
+                 // l + 1's classify fills the other set
+  uint64_t cap0, split_extra;
+  unsigned long long* lcount;  // two counter sets (the level schedule: by level parity)
+  int* err;
+  unsigned int* hnext;  // task counters of the hash launches: [0] main / third stream, [1] aux stream
+};
+// one level's split: its tasks and the chunk / digit / count-matrix bases
+struct SplitBufs {
+  const Task* cur_split;
+  int64_t ns;
+  uint32_t *nch, *ndg, *nen, *hmat, *ctask;
+  uint64_t *chb, *dgb, *mtb, *tot2, *hoff;
+};
+// the lists of one parity with room for capl tasks each; the split list also takes the LDS leaf's hot segments
+// (> 512 words each) and more_split overflow tasks of the hash leaves one level up
+static int get_lists(ReduceRun& r, uint64_t capl, const char* split_name, int parity, uint64_t more_split = 0) {
+  static const char* names[2][N_SORT] = {{"t_sort0", "t_sort1", "t_sort2", "t_sort3", "t_sort4"},
+                                         {"t_sort0b", "t_sort1b", "t_sort2b", "t_sort3b", "t_sort4b"}};
+  Workspace& ws = r.ctx->ws;
+  TaskLists& TL = r.TL;
+  for (int c = 0; c < N_SORT; ++c) OH_TRY(ws.get(names[parity][c], capl * sizeof(Task), reinterpret_cast<void**>(&TL.sort[c])));
+  OH_TRY(ws.get(parity ? "t_hashb" : "t_hash", capl * sizeof(Task), reinterpret_cast<void**>(&TL.hash)));
+  OH_TRY(ws.get(parity ? "t_ldsb" : "t_lds", capl * sizeof(Task), reinterpret_cast<void**>(&TL.lds)));
+  OH_TRY(ws.get(split_name, (capl + r.split_extra + more_split) * sizeof(Task), reinterpret_cast<void**>(&TL.split)));
+  TL.cap = capl;
+  return 0;
+}
+// hash leaves of tasks [lo, hi) of the hash list on stream st, buffer wb0 for buf 0. Overflowing tasks go to
+// ov[*n_ov] (capacity: the launch's tasks) and add their split's work to ov_work, if given; slot: the task counter
+// (launches that can be in flight together take different ones)
+static void launch_hash_range(const ReduceRun& r, uint64_t lo, uint64_t hi, uint32_t* wb0, hipStream_t st, Task* ov,
+                              unsigned long long* n_ov, unsigned long long* ov_work, int slot) {
+  if (hi <= lo) return;
+  const int64_t nh = (int64_t)(hi - lo);
+  const unsigned hg = (unsigned)std::min<int64_t>(nh, r.plan->hash_blocks);
+  unsigned int* nt = r.plan->hgrid == 0 ? nullptr : r.hnext + slot;
+  if (nt) hipMemsetAsync(nt, 0, sizeof(unsigned int), st);
+  with_fom(r.plan->fom, [&](auto M) {
+    k_agg_hash<decltype(M)::value><<<hg, AGG_T, 0, st>>>(r.TL.hash + lo, nh, wb0, r.w1, r.row_key, *r.R, *r.Lt, r.n_rules, r.O,
+                                                         ov, n_ov, r.fo, nt, ov_work);
+  });
+}
+// register sorts of tasks [lo[c], hi[c]) of the sort classes (64 << c words, M = 1 << c per lane) on stream st
+template <int M, int FOM>
+static void launch_sort_class(const ReduceRun& r, const Task* list, uint64_t lo, uint64_t hi, uint32_t* wb0, hipStream_t st) {
+  if (hi <= lo) return;
+  const int64_t n = (int64_t)(hi - lo);
+  const unsigned g = (unsigned)std::min<uint64_t>(ceil_div(n, 4), (uint64_t)r.ctx->n_cu * 32);
+  const size_t lds = FOM == 2 ? (size_t)r.fo.nf * 8 : 0;  // the block's per-file rows
+  k_agg_sort<M, FOM><<<g, 256, lds, st>>>(list + lo, n, wb0, r.w1, r.row_key, *r.R, *r.Lt, r.n_rules, r.Osort, r.fo);
+}
+static void launch_sorts(const ReduceRun& r, const unsigned long long* lo, const unsigned long long* hi, uint32_t* wb0,
+                         hipStream_t st) {
+  with_fom(r.plan->fom, [&](auto F) {
+    constexpr int FOM = decltype(F)::value;
+    launch_sort_class<1, FOM>(r, r.TL.sort[0], lo[0], hi[0], wb0, st);
+    launch_sort_class<2, FOM>(r, r.TL.sort[1], lo[1], hi[1], wb0, st);
+    launch_sort_class<4, FOM>(r, r.TL.sort[2], lo[2], hi[2], wb0, st);
+    launch_sort_class<8, FOM>(r, r.TL.sort[3], lo[3], hi[3], wb0, st);
+    launch_sort_class<16, FOM>(r, r.TL.sort[4], lo[4], hi[4], wb0, st);
+  });
+}
+// LDS leaves of the level's n LDS tasks on the main stream (hot segments are appended to the split list)
+static void launch_lds_leaves(const ReduceRun& r, unsigned long long n) {
+  const unsigned lg = (unsigned)std::min<uint64_t>(n, (uint64_t)r.ctx->n_cu * 4);
+  auto go = [&](auto kern) {
+    kern<<<lg, LDS_T, 0, r.s>>>(r.TL.lds, (int64_t)n, r.wcur0, r.w1, r.row_key, *r.R, *r.Lt, r.O, r.TL.split,
+                                r.lcount + N_SORT + 1, r.TL.cap + r.split_extra, r.err, r.fo);
+  };
+  if (r.plan->FOon) go(k_agg_lds<true>); else go(k_agg_lds<false>);
+}
+// chunks [c0, c1) of a level's split, on the main stream
+static void scatter_chunks(const ReduceRun& r, const SplitBufs& sp, uint32_t c0, uint32_t c1) {
+  if (c1 <= c0) return;
+  const ReducePlan& P = *r.plan;
+  auto go = [&](auto kern, unsigned threads, uint32_t len) {  // len: the shortest (LDS) / longest chunk the kernel takes
+    kern<<<c1 - c0, threads, 0, r.s>>>(sp.cur_split, sp.ns, sp.chb, sp.ctask, sp.mtb, sp.hoff, r.wcur0, r.w1, r.Lt->F, sp.hmat,
+                                       c0, len);
+  };
+  uint32_t max_len = SPLIT_CH;
+  if (P.split_lds) {
+    if (P.lds_t == 512) go(k_split_scatter_lds<512>, 512, P.lds_min); else go(k_split_scatter_lds<SPLIT_LT>, SPLIT_LT, P.lds_min);
+    if (P.lds_min <= 1) return;  // (no chunk is empty)
+    max_len = P.lds_min - 1;
+  }
+  if (P.sub == 8192) go(k_split_scatter<8192>, SPLIT_T, max_len); else go(k_split_scatter<4096>, SPLIT_T, max_len);
+}
+// the split's count pass: chunks, digits and count-matrix entries per task and their bases; totals in sp.tot2[0..2]
+static int split_count(const ReduceRun& r, SplitBufs& sp) {
+  Workspace& ws = r.ctx->ws;
+  const size_t ns = (size_t)sp.ns;
+  int rc;
+  if ((rc = ws.get("sp_nch", ns, &sp.nch)) || (rc = ws.get("sp_ndg", ns, &sp.ndg)) || (rc = ws.get("sp_nen", ns, &sp.nen)) ||
+      (rc = ws.get("sp_chb", ns + 1, &sp.chb)) || (rc = ws.get("sp_dgb", ns + 1, &sp.dgb)) ||
+      (rc = ws.get("sp_mtb", ns + 1, &sp.mtb)) || (rc = ws.get("sp_tot", 6, &sp.tot2)))
+    return rc;
+  k_split_prepare<<<grid_for(sp.ns), 256, 0, r.s>>>(sp.cur_split, sp.ns, sp.nch, sp.ndg, sp.nen);
+  OH_TRY(exclusive_scan_u32(r.ctx, sp.nch, sp.chb, sp.ns, sp.tot2, r.s));
+  OH_TRY(exclusive_scan_u32(r.ctx, sp.ndg, sp.dgb, sp.ns, sp.tot2 + 1, r.s));
+  return exclusive_scan_u32(r.ctx, sp.nen, sp.mtb, sp.ns, sp.tot2 + 2, r.s);
+}
+// the split's histogram pass, once the host knows the totals: the chunks' tasks, the count matrix and its offsets
+static int split_hist(const ReduceRun& r, SplitBufs& sp, int64_t nchunks, int64_t nent) {
+  Workspace& ws = r.ctx->ws;
+  OH_TRY(ws.get("sp_hmat", (size_t)nent, &sp.hmat));
+  OH_TRY(ws.get("sp_hoff", (size_t)nent + 1, &sp.hoff));
+  OH_TRY(ws.get("sp_ctask", (size_t)nchunks, &sp.ctask));
+  k_split_chunk_task<<<grid_for(sp.ns), 256, 0, r.s>>>(sp.chb, sp.nch, sp.ns, sp.ctask);
+  k_split_hist<<<(unsigned)nchunks, SPLIT_T, 0, r.s>>>(sp.cur_split, sp.ns, sp.chb, sp.ctask, sp.mtb, r.wcur0, r.w1, r.Lt->F, sp.hmat);
+  return exclusive_scan_u32(r.ctx, sp.hmat, sp.hoff, nent, sp.hoff + nent, r.s);
+}
+// OTTOHIP_DEBUG on the loop of blocking reads: the level's list counts, then the words of every list
+static void dbg_level_lists(const ReduceRun& r, int level, const unsigned long long* nlist) {
+  fprintf(stderr, "[ottohip] level %d: sort %llu/%llu/%llu/%llu/%llu hash %llu split %llu lds %llu\n", level, nlist[0],
+          nlist[1], nlist[2], nlist[3], nlist[4], nlist[N_SORT], nlist[N_SORT + 1], nlist[N_SORT + 2]);
+  const TaskLists& TL = r.TL;
+  Task* lists[N_LISTS] = {TL.sort[0], TL.sort[1], TL.sort[2], TL.sort[3], TL.sort[4], TL.hash, TL.split, TL.lds};
+  fprintf(stderr, "[ottohip] level %d words:", level);
+  for (int c = 0; c < N_LISTS; ++c) {
+    std::vector<Task> tv(nlist[c]);
+    if (nlist[c]) (void)d2h(tv.data(), lists[c], nlist[c], r.s);
+    unsigned long long sw = 0, mx = 0;
+    for (auto& t : tv) { sw += t.len; mx = std::max<unsigned long long>(mx, t.len); }
+    fprintf(stderr, " %llu(max %llu)", sw, mx);
+    if (c == N_SORT + 1 && !tv.empty()) {  // split tasks: words by log2(len) class
+      unsigned long long hw[40] = {}, hn[40] = {};
+      for (auto& t : tv) { const int b = 63 - __builtin_clzll((unsigned long long)t.len | 1ull); hw[b] += t.len; ++hn[b]; }
+      fprintf(stderr, " [split by log2 len:");
+      for (int b = 0; b < 40; ++b)
+        if (hn[b]) fprintf(stderr, " 2^%d:%llu tasks/%llu words", b, hn[b], hw[b]);
+      fprintf(stderr, "]");
+    }
+  }
+  fprintf(stderr, "\n");
+}
+// OTTOHIP_HASH_PROF: the level's nh hash tasks' profile (r.fo.prof): the summed task time and the ten slowest tasks
+static int hash_prof_report(ReduceRun& r, int level, unsigned long long nh) {
+  std::vector<unsigned long long> pv(2 * nh);
+  OH_TRY(d2h(pv.data(), r.fo.prof, pv.size(), r.s));
+  std::vector<size_t> ord(nh);
+  for (size_t i = 0; i < ord.size(); ++i) ord[i] = i;
+  auto tk = [&](size_t i) { return pv[2 * i + 1] & ~(1ull << 63); };
+  std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return tk(a) > tk(b); });
+  unsigned long long tsum = 0, wsum = 0;
+  for (size_t i = 0; i < ord.size(); ++i) { tsum += tk(i); wsum += (uint32_t)pv[2 * i]; }
+  fprintf(stderr, "[ottohip] hash level %d: %zu tasks, %llu words, %.3f ms summed task time; slowest:", level,
+          ord.size(), wsum, tsum / 1e5);
+  for (size_t i = 0; i < ord.size() && i < 10; ++i)
+    fprintf(stderr, " [len %u rows %u %.3f ms%s]", (uint32_t)pv[2 * ord[i]], (uint32_t)(pv[2 * ord[i]] >> 32),
+            tk(ord[i]) / 1e5, (pv[2 * ord[i] + 1] >> 63) ? " full" : "");
+  fprintf(stderr, "\n");
+  r.fo.prof = nullptr;
+  return 0;
+}
+// The pipelined split behind its first half's classify (chunks [0, cA), digits [0, dA)): the second half is
+// scattered and classified on the main stream while the next level's leaves of the first half's sub-buckets start on
+// the aux stream (hash first, then the register sorts). done[c]: tasks of list c of the next level whose leaves were
+// launched here; *hash_early: its hash leaves run on the aux stream (ev_hash). The host reads the first half's list
+// counts from a snapshot taken before ev_half (into the second counter set, which only the level schedule uses
+// otherwise): the second half's classify raises the live counts before it writes the tasks they count.
+static int split_second_half(ReduceRun& r, const SplitBufs& sp, uint32_t cA, int64_t dA, int64_t nchunks, int64_t ndig,
+                             unsigned long long* done, bool* hash_early) {
+  ottohip_ctx* ctx = r.ctx;
+  hipStream_t s = r.s, s2 = r.s2;
+  unsigned long long* snap = r.lcount + LC_WORDS;
+  OH_HIP(hipMemcpyAsync(snap, r.lcount, LC_WORDS * 8, hipMemcpyDeviceToDevice, s));
+  OH_HIP(hipEventRecord(ctx->ev_half, s));
+  scatter_chunks(r, sp, cA, (uint32_t)nchunks);
+  if (ndig > dA)
+    k_split_classify<<<grid_for(ndig - dA), 256, 0, s>>>(sp.cur_split, sp.ns, sp.dgb, sp.mtb, sp.hoff, ndig, r.TL, r.err, sp.hmat, dA);
+  OH_HIP(hipStreamWaitEvent(ctx->aux2, ctx->ev_half, 0));
+  unsigned long long nA[N_LISTS];
+  OH_TRY(d2h(nA, snap, N_LISTS, ctx->aux2));
+  OH_HIP(hipStreamWaitEvent(s2, ctx->ev_half, 0));
+  uint32_t* wb0 = r.w2 ? r.w2 : r.w0;  // the next level's buffer of buf-0 tasks
+  if (nA[N_SORT]) {
+    launch_hash_range(r, 0, nA[N_SORT], wb0, s2, r.TL.split, r.lcount + N_SORT + 1, nullptr, 1);
+    OH_HIP(hipEventRecord(ctx->ev_hash, s2));
+    *hash_early = true;
+  }
+  const unsigned long long zero[N_LISTS] = {};
+  launch_sorts(r, zero, nA, wb0, s2);
+  for (int c = 0; c <= N_SORT; ++c) done[c] = nA[c];
+  return 0;
+}
+
+// The loop of blocking reads (the default): per level the host reads the list counts, queues the level's leaves
+// (register sorts on the aux stream, hash and LDS leaves on the main stream), reads the counts again (tasks the leaves
+// sent back to the split) and the split's totals after its count pass, and queues the split and the next classify.
+static int reduce_levels_blocking(ReduceRun& r, bool* drained) {
+  const ReducePlan& P = *r.plan;
+  ottohip_ctx* ctx = r.ctx;
+  hipStream_t s = r.s, s2 = r.s2;
+  unsigned long long* lcount = r.lcount;
+  unsigned long long done[N_LISTS] = {};  // the level's tasks whose leaves the pipelined split launched already
+  bool hash_early = false, srcA = true;
+  int herr = 0;
+  for (int level = 0; level < 40; ++level) {
+    r.wcur0 = (level == 0 || !r.w2) ? r.w0 : r.w2;
+    unsigned long long nlist[N_LISTS];
+    OH_TRY(d2h(nlist, lcount, N_LISTS, s));
+    OH_TRY(d2h(&herr, r.err, 1, s));
+    if (herr) { set_error("task list overflow / row too large (err=%d)", herr); return OTTOHIP_ELIMIT; }
+    if (P.dbg) dbg_level_lists(r, level, nlist);
+    // the register-sort tasks of this level run on the aux stream, beside this level's hash and
+    // split on s (VALU-bound sorts next to the LDS/HBM-bound split); their task lists are only
+    // rewritten by the next level's classify, which waits for them (ev_join)
+    hipStream_t ss = s2 ? s2 : s;
+    if (s2) { OH_HIP(hipEventRecord(ctx->ev_fork, s)); OH_HIP(hipStreamWaitEvent(s2, ctx->ev_fork, 0)); }
+    const unsigned long long h0 = done[N_SORT], h1 = nlist[N_SORT];  // the level's hash tasks still to launch
+    const bool hf = P.hash_first && h1 > h0;
+    // tasks that overflow the LDS table are appended to the split list
+    if (hf) launch_hash_range(r, h0, h1, r.wcur0, s, r.TL.split, lcount + N_SORT + 1, nullptr, 0);
+    launch_sorts(r, done, nlist, r.wcur0, ss);
+    if (s2) OH_HIP(hipEventRecord(ctx->ev_join[level & 1], s2));
+    if (nlist[N_SORT + 2]) launch_lds_leaves(r, nlist[N_SORT + 2]);
+    if (h1 > h0) {
+      if (P.hprof) {
+        OH_TRY(r.ctx->ws.get("hash_prof", (size_t)(2 * h1), &r.fo.prof));
+        OH_HIP(hipMemsetAsync(r.fo.prof, 0, 16 * h1, s));
+      }
+      if (!hf) launch_hash_range(r, h0, h1, r.wcur0, s, r.TL.split, lcount + N_SORT + 1, nullptr, 0);
+      if (P.hprof) OH_TRY(hash_prof_report(r, level, h1));
+    }
+    if (hash_early) OH_HIP(hipStreamWaitEvent(s, ctx->ev_hash, 0));  // the early hash leaves' overflow tasks
+    if (nlist[N_SORT] || nlist[N_SORT + 2]) OH_TRY(d2h(nlist, lcount, N_LISTS, s));
+    hash_early = false; for (int c = 0; c < N_LISTS; ++c) done[c] = 0;
+    SplitBufs sp{r.TL.split, (int64_t)nlist[N_SORT + 1]};
+    if (P.dbg) fprintf(stderr, "[ottohip] level %d: split after hash overflow %lld\n", level, (long long)sp.ns);
+    if (sp.ns == 0) {
+      if (s2) OH_HIP(hipStreamWaitEvent(s, ctx->ev_join[level & 1], 0));
+      *drained = true;
+      return 0;
+    }
+    if ((uint64_t)sp.ns > r.TL.cap) { set_error("split list overflow"); return OTTOHIP_ELIMIT; }
+    OH_TRY(split_count(r, sp));
+    if (P.pipe) k_split_half<<<1, 64, 0, s>>>(sp.chb, sp.dgb, sp.ns, sp.tot2, sp.tot2 + 3);  // (task, chunk, digit) of the halves' border
+    uint64_t tt[6] = {0, 0, 0, 0, 0, 0};
+    OH_TRY(d2h(tt, sp.tot2, P.pipe ? 6 : 3, s));
+    const int64_t nchunks = (int64_t)tt[0], ndig = (int64_t)tt[1], nent = (int64_t)tt[2];
+    // pipelined when the split is large and the border falls strictly inside it
+    const bool piped = P.pipe && (uint64_t)nchunks >= P.PIPE_MIN_CHUNKS && tt[3] > 0 && (int64_t)tt[3] < sp.ns &&
+                       tt[4] > 0 && (int64_t)tt[4] < nchunks && tt[5] > 0 && (int64_t)tt[5] < ndig;
+    const uint32_t cA = piped ? (uint32_t)tt[4] : (uint32_t)nchunks;
+    const int64_t dA = piped ? (int64_t)tt[5] : ndig;
+    OH_TRY(split_hist(r, sp, nchunks, nent));
+    scatter_chunks(r, sp, 0, cA);
+    // next lists (a sub-bucket is one task in exactly one list: ndig bounds every list): the other
+    // parity's set, last read by the sorts of level - 1
+    if (s2 && level >= 1) OH_HIP(hipStreamWaitEvent(s, ctx->ev_join[(level + 1) & 1], 0));
+    OH_TRY(get_lists(r, std::max(r.cap0, (uint64_t)ndig), srcA ? "t_splitB" : "t_splitA", (level + 1) & 1));
+    hipMemsetAsync(lcount, 0, LC_WORDS * 8, s);
+    k_split_classify<<<grid_for(dA), 256, 0, s>>>(sp.cur_split, sp.ns, sp.dgb, sp.mtb, sp.hoff, dA, r.TL, r.err, sp.hmat, 0);
+    if (piped) {
+      if (P.pipe_log) fprintf(stderr, "[ottohip] level %d split pipelined at chunk %u of %lld\n", level, cA, (long long)nchunks);
+      OH_TRY(split_second_half(r, sp, cA, dA, nchunks, ndig, done, &hash_early));
+    }
+    srcA = !srcA;
+    if (hipGetLastError() != hipSuccess) { set_error("split launch failed"); return OTTOHIP_EHIP; }
+  }
+  return 0;
+}
+
+// The level schedule ("Level schedule"). Level l's lists and counter set have parity l & 1. At the top of a
+// level the main stream waits for the hash leaves of the level before (third stream), whose overflow tasks and split
+// work were added to this level's set, and the host reads the set once. Then the hash leaves start on the third
+// stream and the register sorts on the aux stream, both behind ev_fork, and the split of the level's split list plus
+// the deferred overflow tasks (each split from the buffer its words are in) runs on the main stream at once.
+// Orderings: the next level's set is zeroed on the main stream before ev_fork, so before this level's classify
+// and hash leaves, which add to it. A parity's lists are rewritten by the classify two levels on, which waits
+// for their sorts (ev_join) and, through the next level's top, for their hash leaves (ev_hash).
+static int reduce_levels_sched(ReduceRun& r, bool* drained) {
+  ottohip_ctx* ctx = r.ctx;
+  OH_TRY(ctx->level_buffer());
+  hipStream_t s = r.s, s2 = r.s2, s3 = ctx->aux2;
+  const unsigned long long* hv = ctx->level_host;
+  Task* ovl[2] = {nullptr, nullptr};  // overflow tasks of the hash leaves, by the parity of their level
+  bool hash_pending = false;
+  for (int level = 0; level < 40; ++level) {
+    const int p = level & 1;
+    unsigned long long *C = r.lcount + p * LC_WORDS, *Cn = r.lcount + (p ^ 1) * LC_WORDS;
+    r.wcur0 = (level == 0 || !r.w2) ? r.w0 : r.w2;
+    if (hash_pending) OH_HIP(hipStreamWaitEvent(s, ctx->ev_hash, 0));
+    hash_pending = false;
+    OH_HIP(hipMemcpyAsync(ctx->level_host, C, LC_WORDS * 8, hipMemcpyDeviceToHost, s));
+    OH_HIP(hipMemsetAsync(Cn, 0, LC_WORDS * 8, s));
+    OH_HIP(hipEventRecord(ctx->ev_fork, s));
+    OH_HIP(hipStreamSynchronize(s));  // the level's one host read
+    if (hv[LC_ERR]) { set_error("task list overflow / row too large (err=%d)", (int)hv[LC_ERR]); return OTTOHIP_ELIMIT; }
+    unsigned long long nlist[N_LISTS];
+    for (int c = 0; c < N_LISTS; ++c) nlist[c] = hv[c];
+    const uint64_t nh = nlist[N_SORT], nov = hv[LC_OVERFLOW];
+    const int64_t nsl = (int64_t)nlist[N_SORT + 1];
+    const int64_t nchunks = (int64_t)hv[LC_CHUNKS], ndig = (int64_t)hv[LC_DIGITS], nent = (int64_t)hv[LC_ENTRIES];
+    if (r.plan->dbg)
+      fprintf(stderr, "[ottohip] level %d: sort %llu/%llu/%llu/%llu/%llu hash %llu split %llu lds %llu overflow %llu "
+              "(chunks %lld digits %lld entries %lld)\n", level, hv[0], hv[1], hv[2], hv[3], hv[4], hv[N_SORT], hv[N_SORT + 1],
+              hv[N_SORT + 2], hv[LC_OVERFLOW], (long long)nchunks, (long long)ndig, (long long)nent);
+    if ((uint64_t)nsl > r.TL.cap) { set_error("split list overflow"); return OTTOHIP_ELIMIT; }
+    if (nh) {  // overflowing tasks: to this parity's overflow list, counted and summed in the next level's set
+      OH_TRY(ctx->ws.get(p ? "t_overB" : "t_overA", (size_t)nh, &ovl[p]));
+      OH_HIP(hipStreamWaitEvent(s3, ctx->ev_fork, 0));
+      launch_hash_range(r, 0, nh, r.wcur0, s3, ovl[p], Cn + LC_OVERFLOW, Cn + LC_CHUNKS, 0);
+      OH_HIP(hipEventRecord(ctx->ev_hash, s3));
+      hash_pending = true;
+    }
+    OH_HIP(hipStreamWaitEvent(s2, ctx->ev_fork, 0));
+    const unsigned long long zero[N_LISTS] = {};
+    launch_sorts(r, zero, nlist, r.wcur0, s2);
+    OH_HIP(hipEventRecord(ctx->ev_join[p], s2));
+    SplitBufs sp{r.TL.split, nsl + (int64_t)nov};
+    if (sp.ns == 0 && !hash_pending) {  // nothing left to split and no overflow to come: both other streams join
+      OH_HIP(hipStreamWaitEvent(s, ctx->ev_join[p], 0));
+      *drained = true;
+      return 0;
+    }
+    if (sp.ns) {
+      // (the list was allocated with room for the overflow of the level before: get_lists(.., nh) below)
+      if (nov)
+        OH_HIP(hipMemcpyAsync(r.TL.split + nsl, ovl[p ^ 1], (size_t)nov * sizeof(Task), hipMemcpyDeviceToDevice, s));
+      OH_TRY(split_count(r, sp));
+      OH_TRY(split_hist(r, sp, nchunks, nent));
+      scatter_chunks(r, sp, 0, (uint32_t)nchunks);
+    }
+    // the next lists: the other parity's set, last read by the sorts (ev_join) and hash leaves (waited for at the
+    // top of this level) of level - 1
+    if (level >= 1) OH_HIP(hipStreamWaitEvent(s, ctx->ev_join[p ^ 1], 0));
+    OH_TRY(get_lists(r, std::max(r.cap0, (uint64_t)ndig), p ? "t_splitA" : "t_splitB", p ^ 1, nh));
+    r.TL.n = Cn;
+    if (sp.ns)
+      k_split_classify<<<grid_for(ndig), 256, 0, s>>>(sp.cur_split, sp.ns, sp.dgb, sp.mtb, sp.hoff, ndig, r.TL,
+                                                     reinterpret_cast<int*>(Cn + LC_ERR), sp.hmat, 0);
+    if (hipGetLastError() != hipSuccess) { set_error("split launch failed"); return OTTOHIP_EHIP; }
+  }
+  return 0;
+}
+
+// the closing statistics: the stripes summed, the conservation check, the table's counts, the file options' results
+static int reduce_finish(ReduceRun& r, ottohip_table* T, const ottohip_file_opts* fopts, uint64_t P, uint64_t n_slots) {
+  hipStream_t s = r.s;
+  const int n_rules = r.n_rules;
+  std::vector<unsigned long long> stv((size_t)STAT_STRIPES * STAT_STRIDE);
+  OH_TRY(d2h(stv.data(), r.O.stats, stv.size(), s));
+  unsigned long long st[STAT_STRIDE] = {};
+  for (int k = 0; k < STAT_STRIPES; ++k)
+    for (int j = 0; j < STAT_STRIDE; ++j) st[j] += stv[(size_t)k * STAT_STRIDE + j];
+  if (hipGetLastError() != hipSuccess) { set_error("reduce failed"); return OTTOHIP_EHIP; }
+  unsigned long long U = 0, dropped = 0;
+  for (int q = 0; q < n_rules; ++q) U += st[q * 4 + 0];
+  const unsigned long long sum_pairs = st[STAT_RAW + 1], raw_rows = st[STAT_RAW];  // stored rows / pairs
+  if (r.plan->FOon) {
+    OH_TRY(d2h(&dropped, r.fo.dropped, 1, s));
+    if (r.fo.dbg) {
+      unsigned long long dv[8];
+      OH_TRY(d2h(dv, r.fo.dbg, 8, s));
+      fprintf(stderr, "[ottohip] file opts: hash dropped %llu kept %llu (loaded %llu inserted %llu), sort dropped %llu kept %llu\n",
+              dv[0], dv[1], dv[4], dv[5], dv[2], dv[3]);
+    }
+    OH_TRY(file_opts_finish(fopts, r.fo, s));
+  }
+  T->n_rows = (int64_t)U;
+  T->n_slots = (int64_t)n_slots;
+  if (sum_pairs + dropped != P || raw_rows > P) {  // conservation: every emitted pair is counted (or cut) exactly once
+    set_error("reduce: %llu pairs counted + %llu cut of %llu emitted (rows %llu)", sum_pairs, dropped,
+              (unsigned long long)P, raw_rows);
+    static const bool warn_only = getenv("OTTOHIP_CONSERVATION_WARN") != nullptr;  // debugging aid
+    if (!warn_only) return OTTOHIP_EHIP;
+    fprintf(stderr, "[ottohip] WARNING %s\n", ottohip_last_error());
+  }
+  for (int q = 0; q < n_rules; ++q)  // (n_rows, n_pairs, file_rows, file_rows_ge2)
+    T->stats[q] = {(int64_t)st[q * 4 + 0], (int64_t)st[q * 4 + 1], (int64_t)st[q * 4 + 2], (int64_t)st[q * 4 + 3]};
+  return 0;
+}
+
+// S5: file options, plan, table buffers, constants, the level-0 classify of the rows, one of the two level loops, the
+// closing statistics. w2: a third word buffer for the split levels >= 1 (level 0 splits w0 -> w1, then w1 <-> w2), so
+// w0 keeps the emitted words (ottohip_file_opts.keep_words); row_base: row_begin values are offsets + row_base
 static int covis_reduce(ottohip_ctx* ctx, uint32_t* w0, uint32_t* w1, uint64_t P, const uint64_t* row_begin,
                         const uint32_t* row_key, int64_t Rn, const RulesDev& R, const Layout& Lt, int n_rules,
                         ottohip_table* T, hipStream_t s, const ottohip_file_opts* fopts = nullptr,
                         const FileOpts* fo_parts = nullptr, uint32_t* w2 = nullptr, uint64_t row_base = 0) {
-  // w2: a third word buffer for the split levels >= 1 (level 0 splits w0 -> w1, then w1 <-> w2), so w0 keeps the
-  // emitted words (ottohip_file_opts.keep_words); row_base: row_begin values are offsets + row_base (a row range)
   Workspace& ws = ctx->ws;
-  int rc;
-  int* err;
-  OH_TRY(ws.get("err", 4, &err));
-  FileOpts fo;
-  memset(&fo, 0, sizeof fo);
+  ReduceRun r{};
+  r.ctx = ctx; r.s = s; r.w0 = w0; r.w1 = w1; r.w2 = w2; r.wcur0 = w0;
+  r.row_key = row_key; r.R = &R; r.Lt = &Lt; r.n_rules = n_rules;
+  OH_TRY(ws.get("err", 4, &r.err));
+  FileOpts& fo = r.fo;
   if (fopts) OH_TRY(file_opts_setup(ctx, fopts, n_rules, R, fo, s));
   if (fo_parts) {  // part mode: tables already on the device; a drop counter for the conservation check
     fo = *fo_parts;
-    OH_TRY(ctx->ws.get("fo_dropped", 1, &fo.dropped));
+    OH_TRY(ws.get("fo_dropped", 1, &fo.dropped));
     OH_HIP(hipMemsetAsync(fo.dropped, 0, 8, s));
   }
-  const bool FOon = fopts != nullptr || fo_parts != nullptr;
-  // per-file rows only (no key cuts, no parts): the register sorts keep their occupancy (k_agg_sort<M, 2>)
-  const bool FOhist = FOon && !fo.cuts && !fo.parts && fo.hist != nullptr;
-  const bool FOmir = FOon && fo.parts && fo.mirror_off != 0;  // part mode with explicit mirror rows
+  ReducePlan plan;
+  OH_TRY(reduce_plan(ctx, fo, fopts != nullptr || fo_parts != nullptr, plan));
+  r.plan = &plan;
+  r.s2 = plan.s2;
   // symmetric rules store one row per unordered pair; the readers produce the mirrors (T->sym_mask)
   // part mode with explicit mirror rows: slots [P, 2P) hold the mirror of the row at slot - P
   const uint64_t n_slots = (fo_parts && fo_parts->mirror_off) ? 2 * P : P;
@@ -799,495 +1285,38 @@ static int covis_reduce(ottohip_ctx* ctx, uint32_t* w0, uint32_t* w1, uint64_t P
     OH_TRY(T->b.alloc(n_slots));
     alloc_log_end(t0, "table", "slots", (size_t)n_slots * 17);
   }
-  unsigned long long *stats, *lcount;
+  unsigned long long* stats;
   OH_TRY(ws.get("stats", (size_t)STAT_STRIPES * STAT_STRIDE, &stats));
-  OH_TRY(ws.get("lcount", 2 * LC_WORDS, &lcount));  // two counter sets, by level parity
+  OH_TRY(ws.get("lcount", 2 * LC_WORDS, &r.lcount));
   hipMemsetAsync(stats, 0, (size_t)STAT_STRIPES * STAT_STRIDE * 8, s);
-  hipMemsetAsync(err, 0, sizeof(int), s);
+  hipMemsetAsync(r.err, 0, sizeof(int), s);
   // rows are written at their task's word offsets; each leaf task marks the rest of its range
   // (rule 0xFF), so the slots need no fill (a debug ablation drops the sort kernels' stores)
-  if (getenv("OTTOHIP_REDUCE_DBG")) hipMemsetAsync(T->b.rule, 0xFF, n_slots, s);
-  OutRows O;
+  if (plan.rdbg_fill) hipMemsetAsync(T->b.rule, 0xFF, n_slots, s);
+  OutRows& O = r.O;
   O.rule = T->b.rule; O.aid = T->b.aid; O.aid_next = T->b.aid_next; O.count = T->b.count; O.count_ge2 = T->b.count_ge2;
   O.cap = n_slots; O.stats = stats;
   T->sym_mask = R.sym_mask;
-  // profiling ablation: OTTOHIP_REDUCE_DBG=1 drops the register-sort kernels' row stores
-  static const int rdbg = getenv("OTTOHIP_REDUCE_DBG") ? atoi(getenv("OTTOHIP_REDUCE_DBG")) : 0;
-  OutRows Osort = O;
-  if (rdbg & 1) Osort.cap = 0;
-  int herr = 0;
-
-  static const int split_mean = getenv("OTTOHIP_SPLIT_MEAN") ? atoi(getenv("OTTOHIP_SPLIT_MEAN")) : SPLIT_MEAN;
-  if (split_mean != SPLIT_MEAN) {
-    const uint32_t v = (uint32_t)std::max(64, split_mean);
-    OH_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_split_mean), &v, sizeof v, 0, hipMemcpyHostToDevice, s));
-    OH_HIP(hipStreamSynchronize(s));
-  }
-  static const char* runs_env = getenv("OTTOHIP_SPLIT_RUNS");  // A/B switch
-  if (runs_env && !strcmp(runs_env, "1")) {
-    const uint32_t v = 1;
-    OH_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_split_runs), &v, sizeof v, 0, hipMemcpyHostToDevice, s));
-    OH_HIP(hipStreamSynchronize(s));
-  }
-  static const char* fuse_env = getenv("OTTOHIP_SPLIT_FUSE");  // A/B switch
-  if (fuse_env && !strcmp(fuse_env, "0")) {
-    const uint32_t v = 0;
-    OH_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_split_fuse), &v, sizeof v, 0, hipMemcpyHostToDevice, s));
-    OH_HIP(hipStreamSynchronize(s));
-  }
-  // LDS leaf (k_agg_lds) for rows and split buckets of (SORT_MAX, LDS_CAP] words, fed by splits of
-  // LDS_SPLIT_MEAN-word buckets (OTTOHIP_LDS_LEAF=1, read per call; default: register sorts of
-  // SPLIT_MEAN-word buckets only)
-  const bool lds_leaf = getenv("OTTOHIP_LDS_LEAF") && !strcmp(getenv("OTTOHIP_LDS_LEAF"), "1");
-  {
-    static int8_t lds_state[64] = {};  // per device (the constants live in each device's code object): 0 unset, 1 off, 2 on
-    int8_t& st = lds_state[ctx->device & 63];
-    if (st != (lds_leaf ? 2 : 1)) {
-      const uint32_t on = lds_leaf ? 1u : 0u;
-      OH_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_lds_leaf), &on, sizeof on, 0, hipMemcpyHostToDevice, s));
-      if (split_mean == SPLIT_MEAN) {
-        const uint32_t v = lds_leaf ? (uint32_t)LDS_SPLIT_MEAN : (uint32_t)SPLIT_MEAN;
-        OH_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_split_mean), &v, sizeof v, 0, hipMemcpyHostToDevice, s));
-      }
-      OH_HIP(hipStreamSynchronize(s));
-      st = lds_leaf ? 2 : 1;
-    }
-  }
-  static const int hash_prio = getenv("OTTOHIP_HASH_PRIO") ? atoi(getenv("OTTOHIP_HASH_PRIO")) : 0;  // A/B switch
-  if (hash_prio) {
-    const uint32_t v = (uint32_t)hash_prio;
-    OH_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_hash_prio), &v, sizeof v, 0, hipMemcpyHostToDevice, s));
-    OH_HIP(hipStreamSynchronize(s));
-  }
+  r.Osort = O;
+  if (plan.rdbg & 1) r.Osort.cap = 0;
+  OH_TRY(reduce_constants(ctx, plan, s));
   int ph = ctx->begin("reduce", s, 4.0 * (double)P);
   // level 0 task lists come from the rows
-  uint64_t cap0 = (uint64_t)std::max<int64_t>(Rn, 1);
-  TaskLists TL;
-  TL.n = lcount;
-  // task lists double-buffered by level parity: level l's sorts (aux stream) may still read theirs
-  // while level l + 1's classify fills the other set
-  const uint64_t split_extra = P / 512 + 64;
-  auto get_lists = [&](uint64_t capl, const char* split_name, int parity, uint64_t more_split = 0) -> int {
-    static const char* names[2][N_SORT] = {{"t_sort0", "t_sort1", "t_sort2", "t_sort3", "t_sort4"},
-                                           {"t_sort0b", "t_sort1b", "t_sort2b", "t_sort3b", "t_sort4b"}};
-    for (int c = 0; c < N_SORT; ++c)
-      if (int r = ws.get(names[parity][c], capl * sizeof(Task), reinterpret_cast<void**>(&TL.sort[c]))) return r;
-    if (int r = ws.get(parity ? "t_hashb" : "t_hash", capl * sizeof(Task), reinterpret_cast<void**>(&TL.hash))) return r;
-    if (int r = ws.get(parity ? "t_ldsb" : "t_lds", capl * sizeof(Task), reinterpret_cast<void**>(&TL.lds))) return r;
-    // the split list also takes the LDS leaf's hot segments (> 512 words each)
-    // (more_split: room behind the list for the overflow tasks of the hash leaves one level up)
-    if (int r = ws.get(split_name, (capl + split_extra + more_split) * sizeof(Task), reinterpret_cast<void**>(&TL.split))) return r;
-    TL.cap = capl;
-    return 0;
-  };
-  if ((rc = get_lists(cap0, "t_splitA", 0))) return rc;
-  const int agg_grid = ctx->n_cu * 8;
-  static const bool overlap = !(getenv("OTTOHIP_REDUCE_OVERLAP") && !strcmp(getenv("OTTOHIP_REDUCE_OVERLAP"), "0"));
-  hipStream_t s2 = nullptr;
-  if (overlap) {
-    OH_TRY(ctx->aux_stream());
-    s2 = ctx->aux;
-  }
-  const char* pipe_env = getenv("OTTOHIP_SPLIT_PIPE");
-  const bool pipe_on = pipe_env && atoi(pipe_env) == 1;
-  // The level schedule (OTTOHIP_REDUCE_SCHED=1, read per call; default 0: the loop of blocking reads further
-  // down): a level's hash leaves run on the third stream and their overflow tasks join the next level's split,
-  // the level's split starts at once, and the host reads one counter set per level. Built and measured, off by
-  // default: the split then shares the CUs with the level's register sorts and ends when it did before (DESIGN
-  // §9). The split pipelining, the LDS leaf and the per-task hash profile are written against the other loop and
-  // select it.
-  const char* sched_env = getenv("OTTOHIP_REDUCE_SCHED");
-  const bool sched = s2 != nullptr && sched_env && atoi(sched_env) == 1 && !pipe_on && !lds_leaf &&
-                     getenv("OTTOHIP_HASH_PROF") == nullptr;
-  // the pushers' error flags: with the level schedule a word of the counter set they push to
-  auto level_err = [&](int set) { return sched ? reinterpret_cast<int*>(lcount + set * LC_WORDS + LC_ERR) : err; };
-  hipMemsetAsync(lcount, 0, 2 * LC_WORDS * 8, s);
-  k_classify_rows<<<grid_for(Rn), 256, 0, s>>>(row_begin, Rn, P, Lt.WB, TL, level_err(0), row_base);
-  // Hash leaf grid (OTTOHIP_HASH_GRID, read per call). Unset: as many blocks as are resident at once (two per CU:
-  // 64 KiB of LDS each), which take their tasks from a device counter; n > 0: n blocks, the same; 0: n_cu * 8
-  // blocks that stride over the tasks (three quarters of them wait for a CU slot behind the register sorts).
-  const char* hgrid_env = getenv("OTTOHIP_HASH_GRID");
-  const int hgrid = hgrid_env ? std::max(0, atoi(hgrid_env)) : -1;
-  const int fom = FOhist ? 2 : (FOmir ? 3 : (FOon ? 1 : 0));
-  unsigned int* hnext = nullptr;  // task counters of the hash launches: [0] main / third stream, [1] aux stream
-  if (hgrid != 0) OH_TRY(ws.get("hash_next", 2, &hnext));
-  if (hgrid < 0 && !ctx->hash_resident[fom]) {
-    int nb = 0;
-    hipError_t e = fom == 2   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_agg_hash<2>, AGG_T, 0)
-                   : fom == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_agg_hash<3>, AGG_T, 0)
-                   : fom == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_agg_hash<1>, AGG_T, 0)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_agg_hash<0>, AGG_T, 0);
-    if (e != hipSuccess || nb < 1) { set_error("k_agg_hash<%d>: occupancy query failed", fom); return OTTOHIP_EHIP; }
-    ctx->hash_resident[fom] = nb * ctx->n_cu;
-  }
-  bool srcA = true;
+  r.cap0 = (uint64_t)std::max<int64_t>(Rn, 1);
+  r.split_extra = P / 512 + 64;
+  r.TL.n = r.lcount;
+  OH_TRY(get_lists(r, r.cap0, "t_splitA", 0));
+  hipMemsetAsync(r.lcount, 0, 2 * LC_WORDS * 8, s);
+  k_classify_rows<<<grid_for(Rn), 256, 0, s>>>(row_begin, Rn, P, Lt.WB, r.TL, plan.sched ? reinterpret_cast<int*>(r.lcount + LC_ERR) : r.err, row_base);
+  if (plan.hgrid != 0) OH_TRY(ws.get("hash_next", 2, &r.hnext));
+  if (plan.dbg) fprintf(stderr, "[ottohip] P=%llu rows=%lld\n", (unsigned long long)P, (long long)Rn);
   bool drained = false;
-  const bool dbg = getenv("OTTOHIP_DEBUG") != nullptr;
-  if (dbg) fprintf(stderr, "[ottohip] P=%llu rows=%lld\n", (unsigned long long)P, (long long)Rn);
-  uint32_t* wcur0 = w0;  // the word buffer of tasks with buf 0 at this level (w2 from level 1 on, if given)
-  // Split pipelining (OTTOHIP_SPLIT_PIPE=1, read per call; off by default: step 57.0-57.3 vs 57.0-57.1 ms same box,
-  // the early leaves and the second half's scatter contend for the same CUs): a large split scatters and classifies its tasks in
-  // two halves; the next level's leaves of the first half's sub-buckets (hash, then register sorts, on the aux
-  // stream) start while the second half is scattered on the main stream. done[c]: tasks of list c of the level
-  // whose leaves were launched that way; hash_early: its hash leaves run on the aux stream (ev_hash).
-  const bool pipe = s2 != nullptr && !lds_leaf && !dbg && getenv("OTTOHIP_HASH_PROF") == nullptr && pipe_on;
-  // splits of >= 2048 chunks (32 M words) are pipelined (OTTOHIP_SPLIT_PIPE_MIN: another bound, for tests)
-  const uint64_t PIPE_MIN_CHUNKS = getenv("OTTOHIP_SPLIT_PIPE_MIN") ? (uint64_t)atoll(getenv("OTTOHIP_SPLIT_PIPE_MIN")) : 2048;
-  unsigned long long done[N_LISTS] = {};
-  bool hash_early = false;
-  // leaves of tasks [lo[c], hi[c]) of the sort classes / [lo[N_SORT], hi[N_SORT]) of the hash list, buffer wb0 for
-  // buf 0
-  // overflowing tasks go to ov[*n_ov] (capacity: the launch's tasks) and add their split's work to ov_work, if given;
-  // slot: the task counter (launches that can be in flight together take different ones)
-  auto launch_hash_range = [&](uint64_t lo, uint64_t hi, uint32_t* wb0, hipStream_t st, Task* ov,
-                               unsigned long long* n_ov, unsigned long long* ov_work, int slot) {
-    if (hi <= lo) return;
-    const int64_t nh = (int64_t)(hi - lo);
-    const Task* th = TL.hash + lo;
-    const int64_t blocks = hgrid == 0 ? (int64_t)agg_grid : (hgrid > 0 ? (int64_t)hgrid : (int64_t)ctx->hash_resident[fom]);
-    const unsigned hg = (unsigned)std::min<int64_t>(nh, blocks);
-    unsigned int* nt = hgrid == 0 ? nullptr : hnext + slot;
-    if (nt) hipMemsetAsync(nt, 0, sizeof(unsigned int), st);
-    if (FOhist)
-      k_agg_hash<2><<<hg, AGG_T, 0, st>>>(th, nh, wb0, w1, row_key, R, Lt, n_rules, O, ov, n_ov, fo, nt, ov_work);
-    else if (FOmir)
-      k_agg_hash<3><<<hg, AGG_T, 0, st>>>(th, nh, wb0, w1, row_key, R, Lt, n_rules, O, ov, n_ov, fo, nt, ov_work);
-    else if (FOon)
-      k_agg_hash<1><<<hg, AGG_T, 0, st>>>(th, nh, wb0, w1, row_key, R, Lt, n_rules, O, ov, n_ov, fo, nt, ov_work);
-    else
-      k_agg_hash<<<hg, AGG_T, 0, st>>>(th, nh, wb0, w1, row_key, R, Lt, n_rules, O, ov, n_ov, fo, nt, ov_work);
-  };
-  auto launch_sorts = [&](const unsigned long long* lo, const unsigned long long* hi, uint32_t* wb0, hipStream_t st) {
-    const unsigned sgrid = (unsigned)ctx->n_cu * 32;
-#define OH_SORT(c, M)                                                                                          \
-    if (hi[c] > lo[c]) {                                                                                       \
-      const int64_t n_ = (int64_t)(hi[c] - lo[c]);                                                             \
-      const Task* t_ = TL.sort[c] + lo[c];                                                                     \
-      const unsigned g_ = (unsigned)std::min<uint64_t>(ceil_div(n_, 4), sgrid);                                \
-      if (FOhist)                                                                                              \
-        k_agg_sort<M, 2><<<g_, 256, (size_t)fo.nf * 8, st>>>(t_, n_, wb0, w1, row_key, R, Lt, n_rules, Osort, fo); \
-      else if (FOmir)                                                                                          \
-        k_agg_sort<M, 3><<<g_, 256, 0, st>>>(t_, n_, wb0, w1, row_key, R, Lt, n_rules, Osort, fo);             \
-      else if (FOon)                                                                                           \
-        k_agg_sort<M, 1><<<g_, 256, 0, st>>>(t_, n_, wb0, w1, row_key, R, Lt, n_rules, Osort, fo);             \
-      else                                                                                                     \
-        k_agg_sort<M><<<g_, 256, 0, st>>>(t_, n_, wb0, w1, row_key, R, Lt, n_rules, Osort, fo);                \
-    }
-    OH_SORT(0, 1) OH_SORT(1, 2) OH_SORT(2, 4) OH_SORT(3, 8) OH_SORT(4, 16)
-#undef OH_SORT
-  };
-  static const int sub = getenv("OTTOHIP_SPLIT_SUB") ? atoi(getenv("OTTOHIP_SPLIT_SUB")) : 4096;  // A/B switch
-  // OTTOHIP_SPLIT_LDS (read per call; 0: off): chunks of >= OTTOHIP_SPLIT_LDS_MIN words (default SPLIT_LDS_MIN) are
-  // scattered by k_split_scatter_lds, a whole chunk staged in LDS; the shorter ones by k_split_scatter as before.
-  // Both kernels run over the same chunks and each leaves the other's at once.
-  const char* lds_env = getenv("OTTOHIP_SPLIT_LDS");
-  const bool split_lds = lds_env ? atoi(lds_env) != 0 : SPLIT_LDS_DEFAULT;
-  const char* ldsmin_env = getenv("OTTOHIP_SPLIT_LDS_MIN");
-  const uint32_t lds_min = (uint32_t)std::min(SPLIT_CH + 1, std::max(0, ldsmin_env ? atoi(ldsmin_env) : SPLIT_LDS_MIN));
-  const int lds_t = getenv("OTTOHIP_SPLIT_LDS_T") ? atoi(getenv("OTTOHIP_SPLIT_LDS_T")) : SPLIT_LT;  // A/B switch
-  // chunks [c0, c1) of a level's split, on the main stream
-  auto scatter_chunks = [&](const Task* cur_split, int64_t ns, const uint64_t* chb, const uint32_t* ctask, const uint64_t* mtb,
-                            const uint64_t* hoff, uint32_t* hmat, uint32_t c0, uint32_t c1) {
-    if (c1 <= c0) return;
-    uint32_t max_len = SPLIT_CH;
-    if (split_lds) {
-      if (lds_t == 512)
-        k_split_scatter_lds<512><<<c1 - c0, 512, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, lds_min);
-      else
-        k_split_scatter_lds<SPLIT_LT><<<c1 - c0, SPLIT_LT, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, lds_min);
-      if (lds_min <= 1) return;  // (no chunk is empty)
-      max_len = lds_min - 1;
-    }
-    if (sub == 8192)
-      k_split_scatter<8192><<<c1 - c0, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, max_len);
-    else
-      k_split_scatter<4096><<<c1 - c0, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, hoff, wcur0, w1, Lt.F, hmat, c0, max_len);
-  };
-  // The level schedule. Level l's lists and counter set have parity l & 1. At the top of a level the main stream
-  // waits for the hash leaves of the level before (third stream), whose overflow tasks and their split work were
-  // added to this level's set, and the host reads the set once: list counts, the split's chunk / digit / entry
-  // totals (summed by the pushers, so the three scans' totals stay on the device), the overflow count and the
-  // error flags. Then the hash leaves start on the third stream and the register sorts on the aux stream, both
-  // behind ev_fork, and the split of the level's split list plus the deferred overflow tasks runs on the main
-  // stream at once. An overflow task keeps its buf: it is split from the buffer its words are in.
-  // Orderings: the next level's set is zeroed on the main stream before ev_fork, so before this level's classify
-  // and hash leaves, which add to it. A parity's lists are rewritten by the classify two levels on, which waits
-  // for their sorts (ev_join) and, through the next level's top, for their hash leaves (ev_hash).
-  auto sched_levels = [&]() -> int {
-    OH_TRY(ctx->level_buffer());
-    hipStream_t s3 = ctx->aux2;
-    const unsigned long long* hv = ctx->level_host;
-    Task* ovl[2] = {nullptr, nullptr};  // overflow tasks of the hash leaves, by the parity of their level
-    bool hash_pending = false;
-    for (int level = 0; level < 40; ++level) {
-      const int p = level & 1;
-      unsigned long long* C = lcount + p * LC_WORDS;
-      unsigned long long* Cn = lcount + (p ^ 1) * LC_WORDS;
-      wcur0 = (level == 0 || !w2) ? w0 : w2;
-      if (hash_pending) OH_HIP(hipStreamWaitEvent(s, ctx->ev_hash, 0));
-      hash_pending = false;
-      OH_HIP(hipMemcpyAsync(ctx->level_host, C, LC_WORDS * 8, hipMemcpyDeviceToHost, s));
-      OH_HIP(hipMemsetAsync(Cn, 0, LC_WORDS * 8, s));
-      OH_HIP(hipEventRecord(ctx->ev_fork, s));
-      OH_HIP(hipStreamSynchronize(s));  // the level's one host read
-      if (hv[LC_ERR]) {
-        set_error("task list overflow / row too large (err=%d)", (int)hv[LC_ERR]);
-        return OTTOHIP_ELIMIT;
-      }
-      unsigned long long nlist[N_LISTS];
-      for (int c = 0; c < N_LISTS; ++c) nlist[c] = hv[c];
-      const uint64_t nh = nlist[N_SORT], nov = hv[LC_OVERFLOW];
-      const int64_t nsl = (int64_t)nlist[N_SORT + 1], ns = nsl + (int64_t)nov;
-      const int64_t nchunks = (int64_t)hv[LC_CHUNKS], ndig = (int64_t)hv[LC_DIGITS], nent = (int64_t)hv[LC_ENTRIES];
-      if (dbg)
-        fprintf(stderr, "[ottohip] level %d: sort %llu/%llu/%llu/%llu/%llu hash %llu split %llu lds %llu overflow %llu "
-                "(chunks %lld digits %lld entries %lld)\n", level, nlist[0], nlist[1], nlist[2], nlist[3], nlist[4],
-                (unsigned long long)nh, nlist[N_SORT + 1], nlist[N_SORT + 2], (unsigned long long)nov, (long long)nchunks,
-                (long long)ndig, (long long)nent);
-      if ((uint64_t)nsl > TL.cap) { set_error("split list overflow"); return OTTOHIP_ELIMIT; }
-      if (nh) {  // overflowing tasks: to this parity's overflow list, counted and summed in the next level's set
-        if ((rc = ws.get(p ? "t_overB" : "t_overA", (size_t)nh, &ovl[p]))) return rc;
-        OH_HIP(hipStreamWaitEvent(s3, ctx->ev_fork, 0));
-        launch_hash_range(0, nh, wcur0, s3, ovl[p], Cn + LC_OVERFLOW, Cn + LC_CHUNKS, 0);
-        OH_HIP(hipEventRecord(ctx->ev_hash, s3));
-        hash_pending = true;
-      }
-      OH_HIP(hipStreamWaitEvent(s2, ctx->ev_fork, 0));
-      const unsigned long long zero[N_LISTS] = {};
-      launch_sorts(zero, nlist, wcur0, s2);
-      OH_HIP(hipEventRecord(ctx->ev_join[p], s2));
-      if (ns == 0 && !hash_pending) {  // nothing left to split and no overflow to come: both other streams join
-        OH_HIP(hipStreamWaitEvent(s, ctx->ev_join[p], 0));
-        drained = true;
-        return 0;
-      }
-      Task* cur_split = TL.split;
-      uint32_t *nch, *ndg, *nen, *hmat = nullptr;
-      uint64_t *chb, *dgb = nullptr, *mtb = nullptr, *tot2, *hoff = nullptr;
-      if (ns) {
-        // (the list was allocated with room for the overflow of the level before: get_lists(.., nh) below)
-        if (nov)
-          OH_HIP(hipMemcpyAsync(cur_split + nsl, ovl[p ^ 1], (size_t)nov * sizeof(Task), hipMemcpyDeviceToDevice, s));
-        uint32_t* ctask;
-        if ((rc = ws.get("sp_nch", (size_t)ns, &nch)) || (rc = ws.get("sp_ndg", (size_t)ns, &ndg)) ||
-            (rc = ws.get("sp_nen", (size_t)ns, &nen)) || (rc = ws.get("sp_chb", (size_t)ns + 1, &chb)) ||
-            (rc = ws.get("sp_dgb", (size_t)ns + 1, &dgb)) || (rc = ws.get("sp_mtb", (size_t)ns + 1, &mtb)) ||
-            (rc = ws.get("sp_tot", 6, &tot2)) || (rc = ws.get("sp_hmat", (size_t)nent, &hmat)) ||
-            (rc = ws.get("sp_hoff", (size_t)nent + 1, &hoff)) || (rc = ws.get("sp_ctask", (size_t)nchunks, &ctask)))
-          return rc;
-        k_split_prepare<<<grid_for(ns), 256, 0, s>>>(cur_split, ns, nch, ndg, nen);
-        if ((rc = exclusive_scan_u32(ctx, nch, chb, ns, tot2, s)) || (rc = exclusive_scan_u32(ctx, ndg, dgb, ns, tot2 + 1, s)) ||
-            (rc = exclusive_scan_u32(ctx, nen, mtb, ns, tot2 + 2, s)))
-          return rc;
-        k_split_chunk_task<<<grid_for(ns), 256, 0, s>>>(chb, nch, ns, ctask);
-        k_split_hist<<<(unsigned)nchunks, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, wcur0, w1, Lt.F, hmat);
-        if ((rc = exclusive_scan_u32(ctx, hmat, hoff, nent, hoff + nent, s))) return rc;
-        scatter_chunks(cur_split, ns, chb, ctask, mtb, hoff, hmat, 0, (uint32_t)nchunks);
-      }
-      // the next lists: the other parity's set, last read by the sorts (ev_join) and hash leaves (waited for at the
-      // top of this level) of level - 1
-      if (level >= 1) OH_HIP(hipStreamWaitEvent(s, ctx->ev_join[p ^ 1], 0));
-      if ((rc = get_lists(std::max(cap0, (uint64_t)ndig), p ? "t_splitA" : "t_splitB", p ^ 1, nh))) return rc;
-      TL.n = Cn;
-      if (ns) k_split_classify<<<grid_for(ndig), 256, 0, s>>>(cur_split, ns, dgb, mtb, hoff, ndig, TL, level_err(p ^ 1), hmat, 0);
-      if (hipGetLastError() != hipSuccess) { set_error("split launch failed"); return OTTOHIP_EHIP; }
-    }
-    return 0;
-  };
-  if (sched) OH_TRY(sched_levels());
-  for (int level = 0; !sched && level < 40; ++level) {
-    wcur0 = (level == 0 || !w2) ? w0 : w2;
-    unsigned long long nlist[N_LISTS];
-    if ((rc = d2h(nlist, lcount, N_LISTS, s))) return rc;
-    if ((rc = d2h(&herr, err, 1, s))) return rc;
-    if (herr) { set_error("task list overflow / row too large (err=%d)", herr); return OTTOHIP_ELIMIT; }
-    if (dbg) {
-      fprintf(stderr, "[ottohip] level %d: sort %llu/%llu/%llu/%llu/%llu hash %llu split %llu lds %llu\n", level, nlist[0],
-              nlist[1], nlist[2], nlist[3], nlist[4], nlist[N_SORT], nlist[N_SORT + 1], nlist[N_SORT + 2]);
-      Task* lists[N_LISTS] = {TL.sort[0], TL.sort[1], TL.sort[2], TL.sort[3], TL.sort[4], TL.hash, TL.split, TL.lds};
-      fprintf(stderr, "[ottohip] level %d words:", level);
-      for (int c = 0; c < N_LISTS; ++c) {
-        std::vector<Task> tv(nlist[c]);
-        if (nlist[c]) (void)d2h(tv.data(), lists[c], nlist[c], s);
-        unsigned long long sw = 0, mx = 0;
-        for (auto& t : tv) { sw += t.len; mx = std::max<unsigned long long>(mx, t.len); }
-        fprintf(stderr, " %llu(max %llu)", sw, mx);
-        if (c == N_SORT + 1 && !tv.empty()) {  // split tasks: words by log2(len) class
-          unsigned long long hw[40] = {}, hn[40] = {};
-          for (auto& t : tv) { const int b = 63 - __builtin_clzll((unsigned long long)t.len | 1ull); hw[b] += t.len; ++hn[b]; }
-          fprintf(stderr, " [split by log2 len:");
-          for (int b = 0; b < 40; ++b)
-            if (hn[b]) fprintf(stderr, " 2^%d:%llu tasks/%llu words", b, hn[b], hw[b]);
-          fprintf(stderr, "]");
-        }
-      }
-      fprintf(stderr, "\n");
-    }
-    // the register-sort tasks of this level run on the aux stream, beside this level's hash and
-    // split on s (VALU-bound sorts next to the LDS/HBM-bound split); their task lists are only
-    // rewritten by the next level's classify, which waits for them (ev_join)
-    hipStream_t ss = s2 ? s2 : s;
-    if (s2) { OH_HIP(hipEventRecord(ctx->ev_fork, s)); OH_HIP(hipStreamWaitEvent(s2, ctx->ev_fork, 0)); }
-    // the level's LDS-hash leaves are queued before its register sorts, so their few long-running
-    // blocks take CU slots before the sorts' many short ones (step -0.5 ms same box; OTTOHIP_HASH_FIRST=0:
-    // sorts first)
-    static const bool hash_first = !(getenv("OTTOHIP_HASH_FIRST") && !strcmp(getenv("OTTOHIP_HASH_FIRST"), "0"));
-    const bool hf = hash_first && nlist[N_SORT] > done[N_SORT];
-    auto launch_hash = [&]() {
-      launch_hash_range(done[N_SORT], nlist[N_SORT], wcur0, s, TL.split, lcount + N_SORT + 1, nullptr, 0);
-    };
-    if (hf) launch_hash();
-    launch_sorts(done, nlist, wcur0, ss);
-    if (s2) OH_HIP(hipEventRecord(ctx->ev_join[level & 1], s2));
-    if (nlist[N_SORT + 2]) {  // LDS leaves (hot segments are appended to the split list)
-      const unsigned lg = (unsigned)std::min<uint64_t>(nlist[N_SORT + 2], (uint64_t)ctx->n_cu * 4);
-      if (FOon)
-        k_agg_lds<true><<<lg, LDS_T, 0, s>>>(TL.lds, (int64_t)nlist[N_SORT + 2], wcur0, w1, row_key, R, Lt, O, TL.split,
-                                             lcount + N_SORT + 1, TL.cap + split_extra, err, fo);
-      else
-        k_agg_lds<<<lg, LDS_T, 0, s>>>(TL.lds, (int64_t)nlist[N_SORT + 2], wcur0, w1, row_key, R, Lt, O, TL.split,
-                                       lcount + N_SORT + 1, TL.cap + split_extra, err, fo);
-    }
-    if (nlist[N_SORT] > done[N_SORT]) {  // tasks that overflow the LDS table are appended to the split list
-      static const bool hprof = getenv("OTTOHIP_HASH_PROF") != nullptr && !hash_first;  // per-task profile (debugging aid)
-      if (hprof) {
-        if ((rc = ws.get("hash_prof", (size_t)(2 * nlist[N_SORT]), &fo.prof))) return rc;
-        OH_HIP(hipMemsetAsync(fo.prof, 0, 16 * nlist[N_SORT], s));
-      }
-      if (!hf) launch_hash();
-      if (hprof) {
-        std::vector<unsigned long long> pv(2 * nlist[N_SORT]);
-        if ((rc = d2h(pv.data(), fo.prof, pv.size(), s))) return rc;
-        std::vector<size_t> ord(nlist[N_SORT]);
-        for (size_t i = 0; i < ord.size(); ++i) ord[i] = i;
-        auto tk = [&](size_t i) { return pv[2 * i + 1] & ~(1ull << 63); };
-        std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return tk(a) > tk(b); });
-        unsigned long long tsum = 0, wsum = 0;
-        for (size_t i = 0; i < ord.size(); ++i) { tsum += tk(i); wsum += (uint32_t)pv[2 * i]; }
-        fprintf(stderr, "[ottohip] hash level %d: %zu tasks, %llu words, %.3f ms summed task time; slowest:", level,
-                ord.size(), wsum, tsum / 1e5);
-        for (size_t i = 0; i < ord.size() && i < 10; ++i)
-          fprintf(stderr, " [len %u rows %u %.3f ms%s]", (uint32_t)pv[2 * ord[i]], (uint32_t)(pv[2 * ord[i]] >> 32),
-                  tk(ord[i]) / 1e5, (pv[2 * ord[i] + 1] >> 63) ? " full" : "");
-        fprintf(stderr, "\n");
-        fo.prof = nullptr;
-      }
-    }
-    if (hash_early) OH_HIP(hipStreamWaitEvent(s, ctx->ev_hash, 0));  // the early hash leaves' overflow tasks
-    if (nlist[N_SORT] || nlist[N_SORT + 2])
-      if ((rc = d2h(nlist, lcount, N_LISTS, s))) return rc;
-    hash_early = false;
-    for (int c = 0; c < N_LISTS; ++c) done[c] = 0;
-    const int64_t ns = (int64_t)nlist[N_SORT + 1];
-    if (dbg) fprintf(stderr, "[ottohip] level %d: split after hash overflow %lld\n", level, (long long)ns);
-    if (ns == 0) {
-      if (s2) OH_HIP(hipStreamWaitEvent(s, ctx->ev_join[level & 1], 0));
-      drained = true;
-      break;
-    }
-    if ((uint64_t)ns > TL.cap) { set_error("split list overflow"); return OTTOHIP_ELIMIT; }
-    Task* cur_split = TL.split;
-    // chunk / digit / count-matrix bases
-    uint32_t *nch, *ndg, *nen;
-    uint64_t *chb, *dgb, *mtb, *tot2;
-    if ((rc = ws.get("sp_nch", (size_t)ns, &nch)) || (rc = ws.get("sp_ndg", (size_t)ns, &ndg)) ||
-        (rc = ws.get("sp_nen", (size_t)ns, &nen)) || (rc = ws.get("sp_chb", (size_t)ns + 1, &chb)) ||
-        (rc = ws.get("sp_dgb", (size_t)ns + 1, &dgb)) || (rc = ws.get("sp_mtb", (size_t)ns + 1, &mtb)) ||
-        (rc = ws.get("sp_tot", 6, &tot2)))
-      return rc;
-    k_split_prepare<<<grid_for(ns), 256, 0, s>>>(cur_split, ns, nch, ndg, nen);
-    if ((rc = exclusive_scan_u32(ctx, nch, chb, ns, tot2, s)) || (rc = exclusive_scan_u32(ctx, ndg, dgb, ns, tot2 + 1, s)) ||
-        (rc = exclusive_scan_u32(ctx, nen, mtb, ns, tot2 + 2, s)))
-      return rc;
-    if (pipe) k_split_half<<<1, 64, 0, s>>>(chb, dgb, ns, tot2, tot2 + 3);  // (task, chunk, digit) of the halves' border
-    uint64_t tt[6] = {0, 0, 0, 0, 0, 0};
-    if ((rc = d2h(tt, tot2, pipe ? 6 : 3, s))) return rc;
-    const int64_t nchunks = (int64_t)tt[0], ndig = (int64_t)tt[1], nent = (int64_t)tt[2];
-    // pipelined when the split is large and the border falls strictly inside it
-    const bool piped = pipe && (uint64_t)nchunks >= PIPE_MIN_CHUNKS && tt[3] > 0 && (int64_t)tt[3] < ns &&
-                       tt[4] > 0 && (int64_t)tt[4] < nchunks && tt[5] > 0 && (int64_t)tt[5] < ndig;
-    const uint32_t cA = piped ? (uint32_t)tt[4] : (uint32_t)nchunks;
-    const int64_t dA = piped ? (int64_t)tt[5] : ndig;
-    uint32_t *hmat, *ctask;
-    uint64_t* hoff;
-    if ((rc = ws.get("sp_hmat", (size_t)nent, &hmat)) || (rc = ws.get("sp_hoff", (size_t)nent + 1, &hoff)) ||
-        (rc = ws.get("sp_ctask", (size_t)nchunks, &ctask)))
-      return rc;
-    k_split_chunk_task<<<grid_for(ns), 256, 0, s>>>(chb, nch, ns, ctask);
-    k_split_hist<<<(unsigned)nchunks, SPLIT_T, 0, s>>>(cur_split, ns, chb, ctask, mtb, wcur0, w1, Lt.F, hmat);
-    if ((rc = exclusive_scan_u32(ctx, hmat, hoff, nent, hoff + nent, s))) return rc;
-    auto scatter = [&](uint32_t c0, uint32_t c1) { scatter_chunks(cur_split, ns, chb, ctask, mtb, hoff, hmat, c0, c1); };
-    scatter(0, cA);
-    // next lists (a sub-bucket is one task in exactly one list: ndig bounds every list): the other
-    // parity's set, last read by the sorts of level - 1
-    if (s2 && level >= 1) OH_HIP(hipStreamWaitEvent(s, ctx->ev_join[(level + 1) & 1], 0));
-    const uint64_t capn = (uint64_t)ndig;
-    if ((rc = get_lists(std::max(cap0, capn), srcA ? "t_splitB" : "t_splitA", (level + 1) & 1))) return rc;
-    hipMemsetAsync(lcount, 0, LC_WORDS * 8, s);
-    k_split_classify<<<grid_for(dA), 256, 0, s>>>(cur_split, ns, dgb, mtb, hoff, dA, TL, err, hmat, 0);
-    if (piped) {
-      if (getenv("OTTOHIP_SPLIT_PIPE_LOG")) fprintf(stderr, "[ottohip] level %d split pipelined at chunk %u of %lld\n", level, cA, (long long)nchunks);
-      // the first half's sub-buckets are classified: its next-level leaves start on the aux stream (hash first,
-      // then the register sorts) while the second half is scattered and classified here
-      OH_HIP(hipEventRecord(ctx->ev_half, s));
-      scatter(cA, (uint32_t)nchunks);
-      if (ndig > dA)
-        k_split_classify<<<grid_for(ndig - dA), 256, 0, s>>>(cur_split, ns, dgb, mtb, hoff, ndig, TL, err, hmat, dA);
-      OH_HIP(hipStreamWaitEvent(ctx->aux2, ctx->ev_half, 0));
-      unsigned long long nA[N_LISTS];
-      if ((rc = d2h(nA, lcount, N_LISTS, ctx->aux2))) return rc;
-      OH_HIP(hipStreamWaitEvent(s2, ctx->ev_half, 0));
-      uint32_t* wb0 = w2 ? w2 : w0;  // the next level's buffer of buf-0 tasks
-      if (nA[N_SORT]) {
-        launch_hash_range(0, nA[N_SORT], wb0, s2, TL.split, lcount + N_SORT + 1, nullptr, 1);
-        OH_HIP(hipEventRecord(ctx->ev_hash, s2));
-        hash_early = true;
-      }
-      const unsigned long long zero[N_LISTS] = {};
-      launch_sorts(zero, nA, wb0, s2);
-      for (int c = 0; c <= N_SORT; ++c) done[c] = nA[c];
-    }
-    srcA = !srcA;
-    if (hipGetLastError() != hipSuccess) { set_error("split launch failed"); return OTTOHIP_EHIP; }
-  }
+  OH_TRY(plan.sched ? reduce_levels_sched(r, &drained) : reduce_levels_blocking(r, &drained));
   ctx->end(ph, s);
   if (!drained) { set_error("reduce: split levels did not converge"); return OTTOHIP_ELIMIT; }
-  std::vector<unsigned long long> stv((size_t)STAT_STRIPES * STAT_STRIDE);
-  if ((rc = d2h(stv.data(), stats, stv.size(), s))) return rc;
-  unsigned long long st[STAT_STRIDE] = {};
-  for (int k = 0; k < STAT_STRIPES; ++k)
-    for (int j = 0; j < STAT_STRIDE; ++j) st[j] += stv[(size_t)k * STAT_STRIDE + j];
-  if (hipGetLastError() != hipSuccess) { set_error("reduce failed"); return OTTOHIP_EHIP; }
-  unsigned long long U = 0, dropped = 0;
-  for (int r = 0; r < n_rules; ++r) U += st[r * 4 + 0];
-  const unsigned long long sum_pairs = st[STAT_RAW + 1], raw_rows = st[STAT_RAW];  // stored rows / pairs
-  if (FOon) {
-    if ((rc = d2h(&dropped, fo.dropped, 1, s))) return rc;
-    if (fo.dbg) {
-      unsigned long long dv[8];
-      if ((rc = d2h(dv, fo.dbg, 8, s))) return rc;
-      fprintf(stderr, "[ottohip] file opts: hash dropped %llu kept %llu (loaded %llu inserted %llu), sort dropped %llu kept %llu\n",
-              dv[0], dv[1], dv[4], dv[5], dv[2], dv[3]);
-    }
-    if ((rc = file_opts_finish(fopts, fo, s))) return rc;
-  }
-  T->n_rows = (int64_t)U;
-  T->n_slots = (int64_t)n_slots;
-  if (sum_pairs + dropped != P || raw_rows > P) {  // conservation: every emitted pair is counted (or cut) exactly once
-    set_error("reduce: %llu pairs counted + %llu cut of %llu emitted (rows %llu)", sum_pairs, dropped,
-              (unsigned long long)P, raw_rows);
-    static const bool warn_only = getenv("OTTOHIP_CONSERVATION_WARN") != nullptr;  // debugging aid
-    if (!warn_only) return OTTOHIP_EHIP;
-    fprintf(stderr, "[ottohip] WARNING %s\n", ottohip_last_error());
-  }
-  for (int r = 0; r < n_rules; ++r) {
-    T->stats[r].n_rows = (int64_t)st[r * 4 + 0];
-    T->stats[r].n_pairs = (int64_t)st[r * 4 + 1];
-    T->stats[r].file_rows = (int64_t)st[r * 4 + 2];
-    T->stats[r].file_rows_ge2 = (int64_t)st[r * 4 + 3];
-  }
-  return 0;
+  return reduce_finish(r, T, fopts, P, n_slots);
 }
+
 
 extern "C" {
 
@@ -1312,15 +1341,7 @@ void ottohip_ctx_destroy(ottohip_ctx* ctx) {
   ctx->ws.release();
   ctx->spare.release();
   dev_trim();
-  if (ctx->aux) {
-    hipStreamDestroy(ctx->aux);
-    if (ctx->aux2) hipStreamDestroy(ctx->aux2);
-    if (ctx->ev_half) hipEventDestroy(ctx->ev_half);
-    if (ctx->ev_hash) hipEventDestroy(ctx->ev_hash);
-    hipEventDestroy(ctx->ev_fork);
-    hipEventDestroy(ctx->ev_join[0]);
-    hipEventDestroy(ctx->ev_join[1]);
-  }
+  ctx->aux_destroy();
   for (auto e : ctx->event_pool) hipEventDestroy(e);
   if (ctx->pinned) hipHostFree(ctx->pinned);
   if (ctx->level_host) hipHostFree(ctx->level_host);
@@ -1576,23 +1597,20 @@ int ottohip_covis_count_opts(ottohip_ctx* ctx, const ottohip_events* ev, const o
   const ottohip_file_opts* fo_eff =
       (opts && (opts->lo_file >= 0 || opts->hi_file >= 0 || opts->file_rows || opts->file_rows_ge2)) ? opts : nullptr;
   const bool keep = opts && opts->keep_words;
-  ottohip_table* T = new_table(ctx, n_rules, params->n_items);
-  auto fail = [&](int rc) { ottohip_table_free(T); return rc; };
-  int rc;
-  if ((rc = covis_front(ctx, ev, params, nullptr, 1, F, s))) return fail(rc);
-  if (F.P == 0) { *out = T; return 0; }
+  TablePtr T = new_table(ctx, n_rules, params->n_items);
+  OH_TRY(covis_front(ctx, ev, params, nullptr, 1, F, s));
+  if (F.P == 0) { *out = T.release(); return 0; }
   uint32_t *w0, *w1, *w2 = nullptr;
-  if ((rc = ctx->ws.get("words0", (size_t)F.P, &w0)) || (rc = ctx->ws.get("words1", (size_t)F.P, &w1))) return fail(rc);
-  if (keep && (rc = ctx->ws.get("words2", (size_t)F.P, &w2))) return fail(rc);
-  if ((rc = covis_emit_words(ctx, F, ev, w0, s))) return fail(rc);
+  OH_TRY(ctx->ws.get("words0", (size_t)F.P, &w0)); OH_TRY(ctx->ws.get("words1", (size_t)F.P, &w1));
+  if (keep) OH_TRY(ctx->ws.get("words2", (size_t)F.P, &w2));
+  OH_TRY(covis_emit_words(ctx, F, ev, w0, s));
   // the slot range of every row type (rows are type-major), for the per-rule readers; read back on first use
   // (queued before the reduce, whose closing statistics read synchronises the stream)
   if (dev_alloc(reinterpret_cast<void**>(&T->type_slots_dev), 4 * sizeof(uint64_t), "type_slots") == hipSuccess) {
     k_type_slots<<<1, 64, 0, s>>>(F.row_key, F.row_begin, F.Rn, F.P, F.Lt.A, T->type_slots_dev);
     for (int r = 0; r < n_rules; ++r) T->rule_type[r] = (int8_t)rules[r].this_type;
   }
-  if ((rc = covis_reduce(ctx, w0, w1, F.P, F.row_begin, F.row_key, F.Rn, F.R, F.Lt, n_rules, T, s, fo_eff, nullptr, w2)))
-    return fail(rc);
+  OH_TRY(covis_reduce(ctx, w0, w1, F.P, F.row_begin, F.row_key, F.Rn, F.R, F.Lt, n_rules, T.get(), s, fo_eff, nullptr, w2));
   if (keep) {  // the table takes the emitted words (w0, untouched by the three-buffer reduce) and the rows
     KeptEmission* K = new KeptEmission();
     K->words = static_cast<uint32_t*>(ctx->ws.take("words0"));
@@ -1601,7 +1619,7 @@ int ottohip_covis_count_opts(ottohip_ctx* ctx, const ottohip_events* ev, const o
     K->P = F.P; K->Rn = F.Rn; K->R = F.R; K->Lt = F.Lt; K->n_rules = n_rules; K->n_files = ev->n_files;
     T->kept = K;
   }
-  *out = T;
+  *out = T.release();
   return 0;
 }
 
@@ -1622,6 +1640,57 @@ __global__ void k_type_span(const uint32_t* __restrict__ rk, const uint64_t* __r
   out[2] = r[0] < Rn ? rb[r[0]] : P; out[3] = r[1] < Rn ? rb[r[1]] : P;
 }
 
+// an ottohip_part_opts against the call's nf files: per file its first part and cut (who: prefix of the error texts)
+static int part_opts_check(const char* who, const ottohip_part_opts* po, int nf, std::vector<uint8_t>& part_of,
+                           std::vector<uint8_t>& cut_of) {
+  if (po->n_parts < 1 || po->n_parts > 254) { set_error("%s: n_parts=%d outside [1, 254]", who, po->n_parts); return OTTOHIP_ELIMIT; }
+  if (po->n_cuts < 0 || po->n_cuts > FO_MAXCUT) { set_error("%s: n_cuts=%d outside [0, %d]", who, po->n_cuts, FO_MAXCUT); return OTTOHIP_ELIMIT; }
+  part_of.assign(nf, 0);
+  cut_of.assign(nf, FO_NOCUT);
+  for (int f = 0; f < nf; ++f) {
+    if (po->first_part[f] < 0 || po->first_part[f] >= po->n_parts) { set_error("%s: first_part[%d] out of range", who, f); return OTTOHIP_EINVAL; }
+    part_of[f] = (uint8_t)po->first_part[f];
+  }
+  for (int c = 0; c < po->n_cuts; ++c) {
+    const int f = po->cut_file[c];
+    if (f < 0 || f >= nf || cut_of[f] != FO_NOCUT || part_of[f] + 1 >= po->n_parts) {
+      set_error("%s: cut %d (file %d) invalid: one cut per file, inside the parts", who, c, f); return OTTOHIP_EINVAL;
+    }
+    cut_of[f] = (uint8_t)c;
+  }
+  return 0;
+}
+
+// the checked part options into the kernels' FileOpts: part mode, the cut keys, and the per-file tables on the device
+static int part_opts_upload(ottohip_ctx* ctx, const ottohip_part_opts* po, const std::vector<uint8_t>& part_of,
+                            const std::vector<uint8_t>& cut_of, hipStream_t s, FileOpts& fo) {
+  const size_t nf = part_of.size();
+  fo.lo_file = fo.hi_file = 0xFFFFFFFFu;
+  fo.nf = (uint32_t)nf;
+  fo.parts = 1;
+  fo.ncut = (uint32_t)po->n_cuts;
+  for (int c = 0; c < po->n_cuts; ++c) fo.cut_key[c] = po->cut_key[c];
+  uint8_t *d_part, *d_cut;
+  OH_TRY(ctx->ws.get("fo_part_of", nf, &d_part)); OH_TRY(ctx->ws.get("fo_cut_of", nf, &d_cut));
+  OH_HIP(hipMemcpyAsync(d_part, part_of.data(), nf, hipMemcpyHostToDevice, s));
+  OH_HIP(hipMemcpyAsync(d_cut, cut_of.data(), nf, hipMemcpyHostToDevice, s));
+  OH_HIP(hipStreamSynchronize(s));  // host vectors
+  fo.part_of = d_part;
+  fo.cut_of = d_cut;
+  return 0;
+}
+
+// a reduced part-mode table, one id per part. Rows and pairs per part are counted when first read (ottohip_table_stats
+// / _copy / _finalize): the part heads do not need them, and the table scan took 4.3 ms per A6 of click_to_click
+static int part_table_finish(ottohip_table* T, int n_parts, hipStream_t s) {
+  T->n_rules = n_parts;
+  for (int p = 0; p < n_parts; ++p) T->stats[p] = ottohip_rule_stats{};
+  T->part_stats_pending = n_parts;
+  OH_HIP(hipEventCreateWithFlags(&T->produced, hipEventDisableTiming));
+  OH_HIP(hipEventRecord(T->produced, s));
+  return 0;
+}
+
 int ottohip_table_count_parts(ottohip_ctx* ctx, const ottohip_table* t, int rule, const ottohip_part_opts* po,
                                          ottohip_table** out, void* stream) {
   if (!ctx || !t || !po || !out || !po->first_part || (po->n_cuts > 0 && (!po->cut_file || !po->cut_key))) {
@@ -1634,21 +1703,9 @@ int ottohip_table_count_parts(ottohip_ctx* ctx, const ottohip_table* t, int rule
   const int nf = K.n_files;
   if (po->n_files != nf) { set_error("table_count_parts: n_files=%d, the count had %d files", po->n_files, nf); return OTTOHIP_EINVAL; }
   if (nf > FO_MAXF) { set_error("table_count_parts: %d files > %d", nf, FO_MAXF); return OTTOHIP_ELIMIT; }
-  if (po->n_parts < 1 || po->n_parts > 254) { set_error("table_count_parts: n_parts=%d outside [1, 254]", po->n_parts); return OTTOHIP_ELIMIT; }
-  if (po->n_cuts < 0 || po->n_cuts > FO_MAXCUT) { set_error("table_count_parts: n_cuts=%d outside [0, %d]", po->n_cuts, FO_MAXCUT); return OTTOHIP_ELIMIT; }
   if (K.Lt.A > 24) { set_error("table_count_parts: n_items > 2^24"); return OTTOHIP_ELIMIT; }
-  std::vector<uint8_t> part_of(nf), cut_of(nf, FO_NOCUT);
-  for (int f = 0; f < nf; ++f) {
-    if (po->first_part[f] < 0 || po->first_part[f] >= po->n_parts) { set_error("table_count_parts: first_part[%d] out of range", f); return OTTOHIP_EINVAL; }
-    part_of[f] = (uint8_t)po->first_part[f];
-  }
-  for (int c = 0; c < po->n_cuts; ++c) {
-    const int f = po->cut_file[c];
-    if (f < 0 || f >= nf || cut_of[f] != FO_NOCUT || part_of[f] + 1 >= po->n_parts) {
-      set_error("table_count_parts: cut %d (file %d) invalid: one cut per file, inside the parts", c, f); return OTTOHIP_EINVAL;
-    }
-    cut_of[f] = (uint8_t)c;
-  }
+  std::vector<uint8_t> part_of, cut_of;
+  OH_TRY(part_opts_check("table_count_parts", po, nf, part_of, cut_of));
   int type = -1, q = -1;
   for (int tt = 0; tt < 3; ++tt)
     for (int qq = 0; qq < K.R.n_of_type[tt]; ++qq)
@@ -1665,45 +1722,25 @@ int ottohip_table_count_parts(ottohip_ctx* ctx, const ottohip_table* t, int rule
   OH_TRY(d2h(sp, span, 4, s));
   const int64_t r0 = (int64_t)sp[0], r1 = (int64_t)sp[1];
   const uint64_t wlo = sp[2], Psub = sp[3] - sp[2];
-  ottohip_table* T = new_table(ctx, 1, t->n_items);
-  auto fail = [&](int rc) { ottohip_table_free(T); return rc; };
+  TablePtr T = new_table(ctx, 1, t->n_items);
   T->n_rules = po->n_parts;
-  if (Psub == 0 || r1 <= r0) { *out = T; return 0; }
-  int rc;
+  if (Psub == 0 || r1 <= r0) { *out = T.release(); return 0; }
   uint32_t *w1, *w2;
-  if ((rc = ws.get("words1", (size_t)Psub, &w1)) || (rc = ws.get("words2", (size_t)Psub, &w2))) return fail(rc);
+  OH_TRY(ws.get("words1", (size_t)Psub, &w1)); OH_TRY(ws.get("words2", (size_t)Psub, &w2));
   FileOpts fo;
   memset(&fo, 0, sizeof fo);
   fo.type = type;
   fo.q = (uint32_t)q;
-  fo.lo_file = fo.hi_file = 0xFFFFFFFFu;
-  fo.nf = (uint32_t)nf;
-  fo.parts = 1;
   fo.qonly = 1;  // the type's other rules' words are skipped (counted as dropped)
   fo.mirror_off = ((K.R.sym_mask >> rule) & 1u) ? Psub : 0ull;
-  fo.ncut = (uint32_t)po->n_cuts;
-  for (int c = 0; c < po->n_cuts; ++c) fo.cut_key[c] = po->cut_key[c];
-  uint8_t *d_part, *d_cut;
-  if ((rc = ws.get("fo_part_of", (size_t)nf, &d_part)) || (rc = ws.get("fo_cut_of", (size_t)nf, &d_cut))) return fail(rc);
-  OH_HIP(hipMemcpyAsync(d_part, part_of.data(), nf, hipMemcpyHostToDevice, s));
-  OH_HIP(hipMemcpyAsync(d_cut, cut_of.data(), nf, hipMemcpyHostToDevice, s));
-  OH_HIP(hipStreamSynchronize(s));  // host vectors
-  fo.part_of = d_part;
-  fo.cut_of = d_cut;
+  OH_TRY(part_opts_upload(ctx, po, part_of, cut_of, s, fo));
   // the kept words are only read: the level-0 split writes w1, the later levels w1 <-> w2
-  if ((rc = covis_reduce(ctx, K.words + wlo, w1, Psub, K.row_begin + r0, K.row_key + r0, r1 - r0, K.R, K.Lt, K.n_rules, T,
-                         s, nullptr, &fo, w2, wlo)))
-    return fail(rc);
+  OH_TRY(covis_reduce(ctx, K.words + wlo, w1, Psub, K.row_begin + r0, K.row_key + r0, r1 - r0, K.R, K.Lt, K.n_rules,
+                      T.get(), s, nullptr, &fo, w2, wlo));
   T->sym_mask = 0;  // explicit rows (the mirrors written by the leaves)
   T->aid_ordered = fo.mirror_off == 0;
-  T->n_rules = po->n_parts;
-  // per part: rows and pairs, counted when first read (ottohip_table_stats / _copy / _finalize): the part heads
-  // (ottohip_table_part_heads) do not need them, and the table scan took 4.3 ms per A6 of click_to_click
-  for (int p = 0; p < po->n_parts; ++p) T->stats[p] = ottohip_rule_stats{};
-  T->part_stats_pending = po->n_parts;
-  OH_HIP(hipEventCreateWithFlags(&T->produced, hipEventDisableTiming));
-  OH_HIP(hipEventRecord(T->produced, s));
-  *out = T;
+  OH_TRY(part_table_finish(T.get(), po->n_parts, s));
+  *out = T.release();
   return 0;
 }
 
@@ -1719,23 +1756,9 @@ int ottohip_covis_count_parts(ottohip_ctx* ctx, const ottohip_events* ev, const 
   const int nf = ev->n_files;
   if (po->n_files != nf) { set_error("count_parts: n_files=%d, the call has %d files", po->n_files, nf); return OTTOHIP_EINVAL; }
   if (nf > FO_MAXF) { set_error("count_parts: %d files > %d per call", nf, FO_MAXF); return OTTOHIP_ELIMIT; }
-  if (po->n_parts < 1 || po->n_parts > 254 || po->n_parts > TABLE_MAX_IDS) {
-    set_error("count_parts: n_parts=%d outside [1, 254]", po->n_parts); return OTTOHIP_ELIMIT;
-  }
-  if (po->n_cuts < 0 || po->n_cuts > FO_MAXCUT) { set_error("count_parts: n_cuts=%d outside [0, %d]", po->n_cuts, FO_MAXCUT); return OTTOHIP_ELIMIT; }
   if (params->n_items > (1 << 24)) { set_error("count_parts: n_items > 2^24"); return OTTOHIP_ELIMIT; }
-  std::vector<uint8_t> part_of(nf), cut_of(nf, FO_NOCUT);
-  for (int f = 0; f < nf; ++f) {
-    if (po->first_part[f] < 0 || po->first_part[f] >= po->n_parts) { set_error("count_parts: first_part[%d] out of range", f); return OTTOHIP_EINVAL; }
-    part_of[f] = (uint8_t)po->first_part[f];
-  }
-  for (int c = 0; c < po->n_cuts; ++c) {
-    const int f = po->cut_file[c];
-    if (f < 0 || f >= nf || cut_of[f] != FO_NOCUT || part_of[f] + 1 >= po->n_parts) {
-      set_error("count_parts: cut %d (file %d) invalid: one cut per file, inside the parts", c, f); return OTTOHIP_EINVAL;
-    }
-    cut_of[f] = (uint8_t)c;
-  }
+  std::vector<uint8_t> part_of, cut_of;
+  OH_TRY(part_opts_check("count_parts", po, nf, part_of, cut_of));
   hipStream_t s = S(stream);
   OH_HIP(hipSetDevice(ctx->device));
   ctx->reset_timing();
@@ -1744,47 +1767,26 @@ int ottohip_covis_count_parts(ottohip_ctx* ctx, const ottohip_events* ev, const 
   // leaves write the mirrors as explicit rows with their own parts at slot + P (the table is then not in aid order)
   const bool sympart = getenv("OTTOHIP_A6_SYMPART") && !strcmp(getenv("OTTOHIP_A6_SYMPART"), "1");
   OH_TRY(setup_rules(rules, n_rules, params, nf, F.R, F.Lt, /*allow_sym=*/sympart));
-  ottohip_table* T = new_table(ctx, n_rules, params->n_items);
-  auto fail = [&](int rc) { ottohip_table_free(T); return rc; };
-  int rc;
-  if ((rc = covis_front(ctx, ev, params, nullptr, 1, F, s))) return fail(rc);
+  TablePtr T = new_table(ctx, n_rules, params->n_items);
+  OH_TRY(covis_front(ctx, ev, params, nullptr, 1, F, s));
   T->n_rules = po->n_parts;
-  if (F.P == 0) { *out = T; return 0; }
+  if (F.P == 0) { *out = T.release(); return 0; }
   uint32_t *w0, *w1;
-  if ((rc = ctx->ws.get("words0", (size_t)F.P, &w0)) || (rc = ctx->ws.get("words1", (size_t)F.P, &w1))) return fail(rc);
-  if ((rc = covis_emit_words(ctx, F, ev, w0, s))) return fail(rc);
+  OH_TRY(ctx->ws.get("words0", (size_t)F.P, &w0)); OH_TRY(ctx->ws.get("words1", (size_t)F.P, &w1));
+  OH_TRY(covis_emit_words(ctx, F, ev, w0, s));
   FileOpts fo;
   memset(&fo, 0, sizeof fo);
   fo.type = rules[0].this_type;
   fo.q = 0;
-  fo.lo_file = fo.hi_file = 0xFFFFFFFFu;
-  fo.nf = (uint32_t)nf;
-  fo.parts = 1;
-  fo.ncut = (uint32_t)po->n_cuts;
-  for (int c = 0; c < po->n_cuts; ++c) fo.cut_key[c] = po->cut_key[c];
-  uint8_t *d_part, *d_cut;
-  if ((rc = ctx->ws.get("fo_part_of", (size_t)nf, &d_part)) || (rc = ctx->ws.get("fo_cut_of", (size_t)nf, &d_cut))) return fail(rc);
-  OH_HIP(hipMemcpyAsync(d_part, part_of.data(), nf, hipMemcpyHostToDevice, s));
-  OH_HIP(hipMemcpyAsync(d_cut, cut_of.data(), nf, hipMemcpyHostToDevice, s));
-  OH_HIP(hipStreamSynchronize(s));  // host vectors
-  fo.part_of = d_part;
-  fo.cut_of = d_cut;
   fo.mirror_off = (F.R.sym_mask & 1u) ? F.P : 0ull;
-  if ((rc = covis_reduce(ctx, w0, w1, F.P, F.row_begin, F.row_key, F.Rn, F.R, F.Lt, n_rules, T, s, nullptr, &fo)))
-    return fail(rc);
+  OH_TRY(part_opts_upload(ctx, po, part_of, cut_of, s, fo));
+  OH_TRY(covis_reduce(ctx, w0, w1, F.P, F.row_begin, F.row_key, F.Rn, F.R, F.Lt, n_rules, T.get(), s, nullptr, &fo));
   if (fo.mirror_off) {
     T->sym_mask = 0;  // explicit rows (the mirrors written by the leaves)
     T->aid_ordered = false;
   }
-  // per part: rows and pairs (file statistics stay 0: the part-wise finalize is told which column to use)
-  T->n_rules = po->n_parts;
-  // per part: rows and pairs, counted when first read (ottohip_table_stats / _copy / _finalize): the part heads
-  // (ottohip_table_part_heads) do not need them, and the table scan took 4.3 ms per A6 of click_to_click
-  for (int p = 0; p < po->n_parts; ++p) T->stats[p] = ottohip_rule_stats{};
-  T->part_stats_pending = po->n_parts;
-  OH_HIP(hipEventCreateWithFlags(&T->produced, hipEventDisableTiming));
-  OH_HIP(hipEventRecord(T->produced, s));
-  *out = T;
+  OH_TRY(part_table_finish(T.get(), po->n_parts, s));
+  *out = T.release();
   return 0;
 }
 
@@ -1809,33 +1811,29 @@ int ottohip_covis_emit(ottohip_ctx* ctx, const ottohip_events* ev, const ottohip
   if (n_files_total < ev->n_files) { set_error("n_files_total < n_files"); return OTTOHIP_EINVAL; }
   for (int f = 0; f < ev->n_files && file_ids; ++f)
     if (file_ids[f] < 0 || file_ids[f] >= n_files_total) { set_error("file_ids[%d] outside [0, n_files_total)", f); return OTTOHIP_EINVAL; }
-  ottohip_emit* E = new ottohip_emit();
+  std::unique_ptr<ottohip_emit, void (*)(ottohip_emit*)> E(new ottohip_emit(), ottohip_emit_free);
   E->n_parts = n_parts;
   E->ev = *ev;
-  int rc;
-  if ((rc = setup_rules(rules, n_rules, params, n_files_total, E->F.R, E->F.Lt, /*allow_sym=*/params->sym != 0))) {
-    delete E;
-    return rc;
-  }
-  if ((rc = covis_front(ctx, ev, params, file_ids, n_parts, E->F, s))) { delete E; return rc; }
+  OH_TRY(setup_rules(rules, n_rules, params, n_files_total, E->F.R, E->F.Lt, /*allow_sym=*/params->sym != 0));
+  OH_TRY(covis_front(ctx, ev, params, file_ids, n_parts, E->F, s));
   E->gen = ctx->gen;
   E->ctx = ctx;
   E->first_row.assign(n_parts + 1, 0);
   E->first_word.assign(n_parts + 1, 0);
   if (E->F.Rn > 0) {
     uint64_t *d_fr, *d_fw;
-    if ((rc = ctx->ws.get("part_first_row", (size_t)n_parts + 1, &d_fr)) ||
-        (rc = ctx->ws.get("part_first_word", (size_t)n_parts + 1, &d_fw))) { delete E; return rc; }
+    OH_TRY(ctx->ws.get("part_first_row", (size_t)n_parts + 1, &d_fr));
+    OH_TRY(ctx->ws.get("part_first_word", (size_t)n_parts + 1, &d_fw));
     k_part_bounds<<<grid_for(E->F.Rn + 1), 256, 0, s>>>(E->F.row_key, E->F.Rn, E->F.Lt.A, (uint32_t)n_parts, d_fr);
     k_part_words<<<grid_for(n_parts + 1), 256, 0, s>>>(d_fr, E->F.row_begin, E->F.Rn, E->F.P, (uint32_t)n_parts, d_fw);
-    if ((rc = d2h(E->first_row.data(), d_fr, (size_t)n_parts + 1, s)) ||
-        (rc = d2h(E->first_word.data(), d_fw, (size_t)n_parts + 1, s))) { delete E; return rc; }
+    OH_TRY(d2h(E->first_row.data(), d_fr, (size_t)n_parts + 1, s));
+    OH_TRY(d2h(E->first_word.data(), d_fw, (size_t)n_parts + 1, s));
   }
   for (int p = 0; p < n_parts; ++p) {
     rows_per_part[p] = (int64_t)(E->first_row[p + 1] - E->first_row[p]);
     words_per_part[p] = (int64_t)(E->first_word[p + 1] - E->first_word[p]);
   }
-  *out = E;
+  *out = E.release();
   return 0;
 }
 
@@ -1888,9 +1886,8 @@ int ottohip_covis_reduce_received_opts(ottohip_ctx* ctx, const ottohip_rule* rul
   // the senders' storage (ottohip_covis_emit with the same params->sym): symmetric rules once per unordered pair
   OH_TRY(setup_rules(rules, n_rules, params, std::max(n_files_total, 1), R, Lt, /*allow_sym=*/params->sym != 0));
   if (n_words >= ((int64_t)1 << 40) || n_pieces >= ((int64_t)1 << 32)) { set_error("received input too large"); return OTTOHIP_ELIMIT; }
-  ottohip_table* T = new_table(ctx, n_rules, params->n_items);
-  auto fail = [&](int rc) { ottohip_table_free(T); return rc; };
-  if (n_words == 0) { *out = T; return 0; }
+  TablePtr T = new_table(ctx, n_rules, params->n_items);
+  if (n_words == 0) { *out = T.release(); return 0; }
   Workspace& ws = ctx->ws;
   const int64_t n = n_pieces;
   uint32_t *key, *val, *k1, *v1, *len, *lsort, *head;
@@ -1905,47 +1902,47 @@ int ottohip_covis_reduce_received_opts(ottohip_ctx* ctx, const ottohip_rule* rul
       (rc = ws.get("pc_dst", (size_t)n, &dst)) || (rc = ws.get("pc_ridx", (size_t)n, &row_idx)) ||
       (rc = ws.get("pc_tot", 4, &tot)) || (rc = ws.get("err", 4, &err)) ||
       (rc = ws.get("row_key", (size_t)n, &row_key)) || (rc = ws.get("row_begin", (size_t)n, &row_begin)))
-    return fail(rc);
+    return rc;
   const int kbits = Lt.A + 2;
   int ph = ctx->begin("assemble", s, 8.0 * (double)n_words + 24.0 * (double)n);
   hipMemsetAsync(err, 0, sizeof(int), s);
   k_piece_keys<<<grid_for(n), 256, 0, s>>>(pieces, n, key, val, len, 3u << Lt.A, err);
   // source offsets of the pieces (received order), then pieces by row key (stable: by source)
-  if ((rc = exclusive_scan_u32(ctx, len, src_off, n, tot, s))) return fail(rc);
+  OH_TRY(exclusive_scan_u32(ctx, len, src_off, n, tot, s));
   uint32_t *ks = key, *vs = val;
-  if ((rc = radix_sort_pairs(ctx, ks, vs, k1, v1, n, kbits, s))) return fail(rc);
+  OH_TRY(radix_sort_pairs(ctx, ks, vs, k1, v1, n, kbits, s));
   k_piece_order<<<grid_for(n), 256, 0, s>>>(ks, vs, len, n, lsort, head);
   if ((rc = exclusive_scan_u32(ctx, lsort, dst, n, tot + 1, s)) || (rc = exclusive_scan_u32(ctx, head, row_idx, n, tot + 2, s)))
-    return fail(rc);
+    return rc;
   uint64_t tt[3];
   int herr = 0;
-  if ((rc = d2h(tt, tot, 3, s)) || (rc = d2h(&herr, err, 1, s))) return fail(rc);
-  if (herr) { set_error("reduce_received: piece row key out of range"); return fail(OTTOHIP_ERANGE); }
+  if ((rc = d2h(tt, tot, 3, s)) || (rc = d2h(&herr, err, 1, s))) return rc;
+  if (herr) { set_error("reduce_received: piece row key out of range"); return OTTOHIP_ERANGE; }
   if ((int64_t)tt[0] != n_words) {
     set_error("reduce_received: pieces hold %llu words, %lld received", (unsigned long long)tt[0], (long long)n_words);
-    return fail(OTTOHIP_EINVAL);
+    return OTTOHIP_EINVAL;
   }
   const uint64_t P = tt[0];
   const int64_t Rn = (int64_t)tt[2];
   uint32_t *w0, *w1;
-  if ((rc = ws.get("words0", (size_t)P, &w0)) || (rc = ws.get("words1", (size_t)P, &w1))) return fail(rc);
+  if ((rc = ws.get("words0", (size_t)P, &w0)) || (rc = ws.get("words1", (size_t)P, &w1))) return rc;
   k_piece_rows<<<grid_for(n), 256, 0, s>>>(ks, head, row_idx, dst, n, row_key, row_begin);
   {
     uint32_t *nch, *cmap;
     uint64_t* cb;
-    if ((rc = ws.get("pc_nch", (size_t)n, &nch)) || (rc = ws.get("pc_cb", (size_t)n, &cb))) return fail(rc);
+    if ((rc = ws.get("pc_nch", (size_t)n, &nch)) || (rc = ws.get("pc_cb", (size_t)n, &cb))) return rc;
     k_piece_nchunks<<<grid_for(n), 256, 0, s>>>(lsort, n, nch);
-    if ((rc = exclusive_scan_u32(ctx, nch, cb, n, tot + 3, s))) return fail(rc);
+    OH_TRY(exclusive_scan_u32(ctx, nch, cb, n, tot + 3, s));
     uint64_t nc = 0;
-    if ((rc = d2h(&nc, tot + 3, 1, s))) return fail(rc);
-    if ((rc = ws.get("pc_cmap", (size_t)std::max<uint64_t>(nc, 1), &cmap))) return fail(rc);
+    OH_TRY(d2h(&nc, tot + 3, 1, s));
+    OH_TRY(ws.get("pc_cmap", (size_t)std::max<uint64_t>(nc, 1), &cmap));
     k_chunk_map<<<grid_for(n), 256, 0, s>>>(nch, cb, n, cmap);
     k_piece_copy<<<grid_for((int64_t)nc, 4), 256, 0, s>>>(cmap, cb, (int64_t)nc, vs, len, src_off, dst, words, w0);
   }
-  if (hipGetLastError() != hipSuccess) { set_error("assemble launch failed"); return fail(OTTOHIP_EHIP); }
+  if (hipGetLastError() != hipSuccess) { set_error("assemble launch failed"); return OTTOHIP_EHIP; }
   ctx->end(ph, s);
-  if ((rc = covis_reduce(ctx, w0, w1, P, row_begin, row_key, Rn, R, Lt, n_rules, T, s, opts))) return fail(rc);
-  *out = T;
+  OH_TRY(covis_reduce(ctx, w0, w1, P, row_begin, row_key, Rn, R, Lt, n_rules, T.get(), s, opts));
+  *out = T.release();
   return 0;
 }
 

@@ -133,10 +133,18 @@ struct Ctx {
         hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ev_join[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ev_join[1], hipEventDisableTiming) != hipSuccess) {
+      aux_destroy();  // aux back to null: a later call fails here again instead of using null handles
       set_error("aux stream creation failed");
       return OTTOHIP_EHIP;
     }
     return 0;
+  }
+  // the streams and events of aux_stream(), as far as they were created
+  void aux_destroy() {
+    for (hipStream_t* st : {&aux, &aux2})
+      if (*st) { (void)hipStreamDestroy(*st); *st = nullptr; }
+    for (hipEvent_t* e : {&ev_half, &ev_hash, &ev_fork, &ev_join[0], &ev_join[1]})
+      if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
   }
   hipEvent_t take_event() {
     if (event_used == event_pool.size()) {

@@ -1,6 +1,7 @@
 // Count-table and context objects shared by the C-ABI translation units (abi.hip, shard.hip).
 #pragma once
 #include <algorithm>
+#include <memory>
 #include "common.h"
 
 using namespace ottohip;
@@ -67,6 +68,19 @@ struct ottohip_table {
   hipEvent_t produced = nullptr; // part-mode tables: recorded on the producer's stream after the reduce; the
                                  // deferred statistics wait on it (the producer may be a non-blocking stream)
 };
+// A count entry point owns its new table until it hands it to the caller (T.release() into *out), so every error
+// return frees it. new_table: an empty table of the context, every rule's type unknown.
+using TablePtr = std::unique_ptr<ottohip_table, void (*)(ottohip_table*)>;
+static inline TablePtr new_table(ottohip_ctx* ctx, int n_rules, int32_t n_items) {
+  TablePtr T(new ottohip_table(), ottohip_table_free);
+  T->device = ctx->device;
+  T->n_rules = n_rules;
+  T->n_items = n_items;
+  T->ctx = ctx;
+  memset(T->stats, 0, sizeof T->stats);
+  memset(T->rule_type, 0xFF, sizeof T->rule_type);  // -1
+  return T;
+}
 // a part-mode table's per-part statistics (rows, pairs per rule byte), counted on first use (abi.hip)
 namespace ottohip {
 int ensure_part_stats(const ottohip_table* t);
